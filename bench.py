@@ -1,10 +1,18 @@
 """Benchmark of the contrastive-training + dense-retrieval hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--part all|train|scan]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--part all|train|scan|...]
 
 For N>1 the driver launches one process per GPU (torch.distributed.run); each
 rank reads RANK/LOCAL_RANK/WORLD_SIZE and RCCL (backend "nccl") carries the
 collectives.  Rank 0 prints ONE JSON line.
+
+A plain run sets up the C2 training step, warms it up, times K steps and prints the
+headline line (`value` = pairs/s, `ms_per_step` = one timed step).  --full adds
+every other leg below, the GEMM-level roofline passes and the CPU baselines, and
+writes the legs' full objects to bench_detail.json.  --dump-outputs DIR writes what
+the last timed training step produced (dump_outputs) for an output-for-output
+comparison of two builds: the inputs are seeded and identical from run to run.
 
 Metric (BASELINE.json): "query-doc pairs/sec (train) + queries/sec @ top-k over
 N docs".  `value` = training pairs/s (whole job); `retrieval` = queries/s.
@@ -180,11 +188,43 @@ def _live_events(lib, name, fn, n):
     return _prof(lib, name)
 
 
-def run_train(args, rank, world, dev, weights="bf16", cfg=None):
+DUMP_MAX_ELEMS = 4 << 20  # --dump-outputs: at most 4 Mi values (16 MB as float32) per array
+
+
+def dump_outputs(out_dir, model, st):
+    """--dump-outputs: what the last timed training step handed its caller, one
+    <name>.npy each (float32; the scalars float64): the step's loss and gradient norm
+    and the state it left behind -- the query head's parameters after the Adam step,
+    the momentum (key) head's after the momentum update, and the key queue after the
+    enqueue.  An array above DUMP_MAX_ELEMS is written as a fixed sample of its
+    flattened values (indices drawn once from seed 0, sorted), so two builds dump the
+    same positions and the files stay below 64 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, t, dtype=np.float32):
+        a = torch.as_tensor(t).detach().float().cpu().numpy().astype(dtype)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+    save("loss", torch.as_tensor(st.loss_record[-1]).reshape(1), np.float64)
+    if st.grad_norm is not None:  # the optimizer's device tensor [norm, coef, gate, -]
+        save("grad_norm", st.grad_norm.reshape(-1)[:1], np.float64)
+    save("encoder_q_params", model.encoder_q.flat)
+    if getattr(model, "use_momentum", False):
+        save("encoder_k_params", model.encoder_k.flat)
+    if getattr(model, "use_queue", False):
+        save("queue", model.queue)
+
+
+def run_train(args, rank, world, dev, weights="bf16", cfg=None, profile=True, dump_dir=None):
     """weights "fp8": config C5 -- the frozen encoder's nn.Linear layers on e4m3
     (irc_gemm_mx: MX-fp8, e4m3 codes with one E8M0 scale per 32 k, inputs quantised by
     their producing LayerNorm / attention / GELU epilogues); same step.
-    cfg: c2_config() (default) or c4_config() (BERT-large encoder)."""
+    cfg: c2_config() (default) or c4_config() (BERT-large encoder).
+    profile=False: the timed steps alone (a plain run), without the two further passes
+    that price the GEMM launches; dump_dir: --dump-outputs of the last timed step."""
     from irc_amd import _lib
     from src.model import build_model, get_optimizer
     from src.train import TrainState
@@ -232,28 +272,34 @@ def run_train(args, rank, world, dev, weights="bf16", cfg=None):
         dist.barrier()
     dt = time.perf_counter() - t0
     dt = _max_over_ranks(dt, dev, world)
-    live_s, live_n, live_flops = _live_events(lib, gname, step, args.steps)
-    # Kernel efficiency: the same steps once more, serialised (BERT features and
-    # every side-stream launch on the current stream, no prefetch), so concurrent
-    # streams do not stretch the GEMM launches' event durations; the overlapped
-    # (live) figure is reported beside it.
-    model.features_ready(pending[0])
-    torch.cuda.synchronize()
-    from irc_amd._torch import serial_streams
-
-    lib.irc_prof_reset()
-    lib.irc_prof_enable(1)
-    with serial_streams():  # one stream: every GEMM runs alone
-        for _ in range(args.steps):
-            st.micro_batch(TRAIN_B, lambda: model.forward_features(
-                *model.bert_extract_ids(ids, mask, TRAIN_B)), sync_loss=False)
-        torch.cuda.synchronize()
-    lib.irc_prof_enable(0)
-    g_s, g_n, g_flops = _prof(lib, gname)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, model, st)
     large = "large" in str((cfg or {}).get("bert", {}).get("name", ""))
     # PMC traffic of THIS leg's GEMMs (profiles/pmc_<tag>.json; null when absent)
     ptag = ("gemm_bf16_c4" if large else gname) if weights == "bf16" else "gemm_mx"
-    g_bytes = _alg_bytes(lib, _pmc_traffic(ptag), gname + "_bytes")
+    if profile:
+        live_s, live_n, live_flops = _live_events(lib, gname, step, args.steps)
+        # Kernel efficiency: the same steps once more, serialised (BERT features and
+        # every side-stream launch on the current stream, no prefetch), so concurrent
+        # streams do not stretch the GEMM launches' event durations; the overlapped
+        # (live) figure is reported beside it.
+        model.features_ready(pending[0])
+        torch.cuda.synchronize()
+        from irc_amd._torch import serial_streams
+
+        lib.irc_prof_reset()
+        lib.irc_prof_enable(1)
+        with serial_streams():  # one stream: every GEMM runs alone
+            for _ in range(args.steps):
+                st.micro_batch(TRAIN_B, lambda: model.forward_features(
+                    *model.bert_extract_ids(ids, mask, TRAIN_B)), sync_loss=False)
+            torch.cuda.synchronize()
+        lib.irc_prof_enable(0)
+        g_s, g_n, g_flops = _prof(lib, gname)
+        g_bytes = _alg_bytes(lib, _pmc_traffic(ptag), gname + "_bytes")
+    else:  # no GEMM-level figures: they take the two passes above
+        live_s = live_flops = g_s = g_n = g_flops = 0
+        g_bytes = {"alg_bytes_per_launch": None, "traffic_over_alg": None}
     flops_pair = 2 * model.bert_model.flops_per_sequence(TRAIN_L) + _lstm_flops_per_pair(cfg)
     pairs = TRAIN_B * args.steps * world
     achieved = g_flops / g_s / 1e12 if g_s > 0 else None
@@ -833,7 +879,17 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=2)
     ap.add_argument("--scan-depth", type=int, default=SCAN_DEPTH,
                     help="query batches in flight in the retrieval legs")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg (--part), the roofline passes and the CPU baselines; "
+                         "without it only the C2 training step is set up, warmed up and timed")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the C2 training step's last timed step produced to "
+                         "DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if not args.full and args.part != "all":
+        ap.error("--part selects among the legs of a --full run")
+    if args.dump_outputs and args.part not in ("all", "train"):
+        ap.error("--dump-outputs writes the C2 training leg's outputs (--part all or train)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(_launch_ranks(args.gpus))
@@ -860,8 +916,12 @@ def main():
 
     train = scan = None
     model = None
+    if not args.full:  # a plain run: the headline figure's steps and nothing beside them
+        args.part = "train"
+        args.no_cpu_baseline = True
     if args.part in ("all", "train"):
-        model, train = run_train(args, rank, world, dev)
+        model, train = run_train(args, rank, world, dev, profile=args.full,
+                                 dump_dir=args.dump_outputs)
     train8 = None
     if args.part in ("all", "train_fp8"):
         _, train8 = run_train(args, rank, world, dev, weights="fp8")
@@ -992,7 +1052,8 @@ def main():
             scan_fp8["workload"] = (f"C5 retrieval shard: {FP8_N_PER_GPU} e4m3 docs/GPU "
                                     f"(5M over 8 GPUs), {C5_Q} queries, top-{SCAN_K}")
             line["retrieval_fp8"] = scan_fp8
-        print(json.dumps(_compact(line)), flush=True)
+        # a plain run's line is short already and leaves no detail file behind
+        print(json.dumps(_compact(line) if args.full else line), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

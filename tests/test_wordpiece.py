@@ -180,17 +180,21 @@ def _vocab_worker(n):
     return synthetic_vocab_file(n)
 
 
-def test_synthetic_vocab_file_concurrent_writers():
+def test_synthetic_vocab_file_concurrent_writers(monkeypatch, tmp_path):
     """Ranks that start together all create the synthetic vocab file: each writes its
     own temporary copy and renames it into place, so none fails on a rename (the
-    2-rank DP test once did) and the file holds the full vocabulary."""
+    2-rank DP test once did) and the file holds the full vocabulary.  The workers'
+    temporary directory is the test's own (TMPDIR, inherited by the spawned
+    processes): in the shared one the file may be another user's, which this
+    test could not remove."""
     import multiprocessing as mp
     import tempfile
 
     n = 101
+    monkeypatch.setenv("TMPDIR", str(tmp_path))
+    monkeypatch.setattr(tempfile, "tempdir", None)  # re-read TMPDIR here too
     path = os.path.join(tempfile.gettempdir(), f"irc_synthetic_vocab_{n}.txt")
-    if os.path.exists(path):
-        os.remove(path)
+    assert os.path.dirname(path) == str(tmp_path) and not os.path.exists(path)
     ctx = mp.get_context("spawn")
     with ctx.Pool(4) as pool:
         paths = pool.map(_vocab_worker, [n] * 16)

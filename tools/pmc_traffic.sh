@@ -3,6 +3,7 @@
 # rocprofv3 pass per bench part (counters only, no tracing domains), then
 # tools/pmc_summary.py -> gpurun_out/pmc/pmc_<tag>.json (copied to profiles/ by hand).
 cd "$GRAFT_REPO_ROOT" || exit 1
+ROOT=$(pwd)
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc
 mkdir -p $OUT
@@ -10,7 +11,7 @@ cd /tmp
 for part in ${PMC_PARTS:-scan_c2 train bert train_fp8}; do
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 300 rocprofv3 --pmc $c --output-format csv -d $OUT/${part}_$c -o run -- \
-      python3 $GRAFT_REPO_ROOT/bench.py --part $part --steps 3 --warmup 1 --no-cpu-baseline \
+      python3 "$ROOT/bench.py" --full --part $part --steps 3 --warmup 1 --no-cpu-baseline \
       > $OUT/${part}_$c.log 2>&1 || { echo "pass $part $c failed"; exit 1; }
   done
 done
