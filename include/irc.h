@@ -85,6 +85,30 @@ int irc_topk_merge(const float* in_score, const int64_t* in_idx, int64_t P, int6
                    int64_t kin, int64_t kout, float* out_score, int64_t* out_idx,
                    irc_stream_t stream);
 
+/* Candidate-restricted dense top-k: the reference's two-stage predict(), the hashed
+ * n-gram filter documents_filtering (src/evaluation.py:57-83) feeding the dense scoring
+ * its tail sketches (:110-112).  Replaces the host loop over each claim's candidate docs.
+ *
+ * queries [Q, D] bf16; docs [N, D] bf16, one shard whose first global id is doc_offset
+ * (doc_offset + N < 2^31).  cand holds GLOBAL doc ids (int32), query q owning
+ * cand[cand_off[q] .. cand_off[q + 1]); n_cand = cand_off[Q].  Ids are unique within a
+ * list (irc_csr_union_emit writes them ascending and unique); their order does not change
+ * the result.  An id outside [doc_offset, doc_offset + N) belongs to another shard: it is
+ * never read and never eligible, so per-shard results merge with irc_topk_merge as scan
+ * shards do.  score = <q, doc>, bf16 products exact, fp32 accumulation in one fixed order
+ * per (query, doc), whatever the doc's place in the list.  Outputs per query: the eligible
+ * candidates by (score desc, global id asc), irc_scan_topk's rule (NaN lowest, -0 = +0);
+ * slots past the eligible count are (-inf, -1); out_n[q] = min(k, eligible).  Exact.
+ * D as irc_scan_topk accepts, 1 <= k <= 1024; Q > 0 with n_cand == 0 fills the outputs
+ * with padding.  The workspace holds one 64-bit key per candidate.
+ * irc_rerank_chunk: the candidates one scoring workgroup takes (test / tuning aid). */
+int64_t irc_rerank_topk_workspace(int64_t Q, int64_t n_cand, int64_t k);
+int irc_rerank_topk(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,
+                    const int32_t* cand, const int64_t* cand_off, int64_t n_cand, int64_t k,
+                    int64_t doc_offset, void* workspace, int64_t workspace_bytes,
+                    float* out_score, int64_t* out_idx, int32_t* out_n, irc_stream_t stream);
+int irc_rerank_chunk(void);
+
 /* Raw score tile for tests / diagnostics: out[Q, N] fp32 = queries . docs^T
  * using the same MFMA path as irc_scan_topk. */
 int irc_scan_scores(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,

@@ -1,0 +1,475 @@
+// Candidate-restricted dense top-k for gfx950 (MI355X): sparse filter, dense rerank.
+//
+// Joins the two stages of the reference's predict(): the hashed n-gram filter
+// documents_filtering (src/evaluation.py:57-83) leaves each claim's candidate docs as a
+// CSR pair, and the dense scoring its tail sketches (:110-112) ranks exactly those docs --
+// a doc the filter excluded can never enter the top-k, unlike a scan of the whole shard.
+//
+// Design:
+//  * rerank_score_kernel walks the FLATTENED candidate array in chunks of RR_CHUNK, one
+//    workgroup per chunk, whatever the list lengths: one 200k-candidate list spreads over
+//    800 workgroups instead of serialising on one while the short lists finish early.  A
+//    chunk may span several lists; every thread finds the owner of its own candidate by
+//    binary search in cand_off (narrowed first to the chunk's first / last owner).
+//  * Rows are gathered whole: 8 lanes share a row, lane s reads the 16-byte pieces s,
+//    s + 8, ... (8 x 16 B = one 128-byte granule per step, every D % 64 == 0), 8 rows in
+//    flight per wave, 4 waves per workgroup, up to 4 workgroups per CU.  The query slice of
+//    the 8-lane group stays in registers while consecutive rows belong to one query.
+//  * The sum over D has ONE order per (query, doc): each lane accumulates its pieces in
+//    ascending order in one fp32 chain, then lanes combine by xor-shuffles 1, 2, 4.  It
+//    does not depend on the doc's place in the list or on the workgroup (bf16 products are
+//    exact in fp32).  No atomics on scores.
+//  * Every candidate gets a 64-bit key (make_key: score, ~global id) in the workspace,
+//    8 B written against D * 2 read; ids of other shards get key 0 and are never read.
+//  * rerank_select_kernel: one workgroup per query, exact radix select of the k-th key
+//    below the keys' common prefix, then a bitonic sort of the winners.  A list of up to
+//    S_STAGE keys is read from global memory once and selected in LDS; a longer one is
+//    re-read per digit until the selected bucket fits, and the pass that moves the bucket
+//    to LDS also collects the keys above it, so nothing is read after that.  Keys are
+//    distinct (unique ids), so exactly min(k, eligible) keys reach the k-th.
+#include <stdint.h>
+
+#include "irc_common.h"
+
+namespace irc {
+namespace rerank {
+
+constexpr int RR_CHUNK = 256;  // candidates per scoring workgroup (= its threads)
+constexpr int RR_LPR = 8;      // lanes sharing one row
+constexpr int RR_MAXK = 1024;
+constexpr int SNT = 1024;      // select: threads per query
+constexpr int S_STAGE = 8192;  // keys staged in LDS (64 KB)
+constexpr int S_U = 16;        // key loads in flight per thread
+constexpr int S_NH = 4;        // histogram copies (waves w, w + 4, ... share one)
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// acc += <a, b> over the 8 bf16 pairs of one 16-byte piece, element order 0..7
+__device__ __forceinline__ float dot8(u32x4 a, u32x4 b, float acc) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    acc = fmaf(__uint_as_float(a[j] << 16), __uint_as_float(b[j] << 16), acc);
+    acc = fmaf(__uint_as_float(a[j] & 0xffff0000u), __uint_as_float(b[j] & 0xffff0000u), acc);
+  }
+  return acc;
+}
+
+// number of q in [lo, hi) with cand_off[q + 1] <= i, plus lo: the owner of flat
+// candidate i when it lies in [lo, hi]
+__device__ __forceinline__ int owner_of(const int64_t* __restrict__ cand_off, int lo, int hi,
+                                        int64_t i) {
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (cand_off[mid + 1] <= i) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+template <int D>
+__global__ __launch_bounds__(RR_CHUNK) void rerank_score_kernel(
+    const unsigned short* __restrict__ queries, const unsigned short* __restrict__ docs, int Q,
+    int64_t N, const int32_t* __restrict__ cand, const int64_t* __restrict__ cand_off,
+    int64_t n_cand, int64_t doc_offset, uint64_t* __restrict__ keys) {
+  constexpr int NC = D / 64;  // 16-byte pieces per lane per row
+  const int tid = threadIdx.x;
+  const int sub = tid & (RR_LPR - 1);
+  const int64_t i0 = (int64_t)blockIdx.x * RR_CHUNK;
+  const int64_t i = i0 + tid;
+  const int64_t ilast = (i0 + RR_CHUNK <= n_cand ? i0 + RR_CHUNK : n_cand) - 1;
+
+  // the chunk's first and last owner (two independent searches, one latency), then this
+  // thread's own within that range: nothing left to search inside one long list
+  int qa, qb;
+  {
+    int lo_a = 0, hi_a = Q, lo_b = 0, hi_b = Q;
+    while (lo_a < hi_a || lo_b < hi_b) {
+      if (lo_a < hi_a) {
+        const int mid = (lo_a + hi_a) >> 1;
+        if (cand_off[mid + 1] <= i0) lo_a = mid + 1;
+        else hi_a = mid;
+      }
+      if (lo_b < hi_b) {
+        const int mid = (lo_b + hi_b) >> 1;
+        if (cand_off[mid + 1] <= ilast) lo_b = mid + 1;
+        else hi_b = mid;
+      }
+    }
+    qa = lo_a;
+    qb = lo_b;
+  }
+  int myq = 0;
+  int myrow = -1;  // row in this shard, -1: not scored (past the end / another shard)
+  uint32_t gid = 0;
+  if (i < n_cand) {
+    myq = owner_of(cand_off, qa, qb, i);
+    myq = myq < Q - 1 ? myq : Q - 1;  // cand_off[Q] < n_cand (caller's error): stay in bounds
+    const int64_t id = (int64_t)cand[i];
+    const int64_t r = id - doc_offset;
+    if (r >= 0 && r < N) {
+      myrow = (int)r;
+      gid = (uint32_t)id;
+    }
+  }
+
+  // group g = tid / 8 scores candidates 8 g .. 8 g + 7 one after the other, its 8 lanes
+  // sharing each row; lane s keeps the score of candidate 8 g + s
+  u32x4 qv[NC];
+  int qcur = -1;
+  float myscore = 0.f;
+#pragma unroll 1
+  for (int r = 0; r < RR_LPR; ++r) {
+    const int row = __shfl(myrow, r, RR_LPR);
+    const int qq = __shfl(myq, r, RR_LPR);
+    float acc = 0.f;
+    if (row >= 0) {  // uniform over the 8-lane group
+      if (qq != qcur) {
+        const u32x4* qp =
+            reinterpret_cast<const u32x4*>(queries + (int64_t)qq * D) + sub;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) qv[c] = qp[c * RR_LPR];
+        qcur = qq;
+      }
+      const u32x4* dp = reinterpret_cast<const u32x4*>(docs + (int64_t)row * D) + sub;
+      u32x4 dv[NC];
+#pragma unroll
+      for (int c = 0; c < NC; ++c) dv[c] = dp[c * RR_LPR];
+#pragma unroll
+      for (int c = 0; c < NC; ++c) acc = dot8(qv[c], dv[c], acc);
+    }
+    // every lane takes part (the exchange stays inside the 8-lane group)
+    acc += __shfl_xor(acc, 1, 64);
+    acc += __shfl_xor(acc, 2, 64);
+    acc += __shfl_xor(acc, 4, 64);
+    if (sub == r) myscore = acc;
+  }
+  if (i < n_cand) keys[i] = myrow >= 0 ? make_key(myscore, gid) : 0ull;
+}
+
+__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint64_t t = __shfl_xor(v, o, 64);
+    v = t < v ? t : v;
+  }
+  return v;
+}
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint64_t t = __shfl_xor(v, o, 64);
+    v = t > v ? t : v;
+  }
+  return v;
+}
+
+// One workgroup per query over keys[cand_off[q] .. cand_off[q + 1]) (0 = not eligible):
+// the min(k, eligible) largest keys, sorted descending, decoded into the outputs.
+__global__ __launch_bounds__(SNT) void rerank_select_kernel(
+    const uint64_t* __restrict__ keys, const int64_t* __restrict__ cand_off, int64_t n_cand,
+    int k, float* __restrict__ out_score, int64_t* __restrict__ out_idx,
+    int32_t* __restrict__ out_n) {
+  __shared__ uint32_t hist[S_NH][256];
+  __shared__ uint64_t s_key[RR_MAXK];
+  __shared__ uint64_t c_key[S_STAGE];
+  __shared__ uint64_t s_mn[SNT / 64], s_mx[SNT / 64];
+  // 0: eligible count, 1: kr, 2: digit, 3: collect counter, 4: selected bucket size,
+  // 5: staged count
+  __shared__ uint32_t s_misc[6];
+  const int64_t q = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int64_t c0 = cand_off[q], c1 = cand_off[q + 1];
+  c1 = c1 < n_cand ? c1 : n_cand;  // keys[] holds n_cand entries whatever cand_off says
+  c0 = c0 < 0 ? 0 : c0;
+  c0 = c0 < c1 ? c0 : c1;
+  // unordered pass over the list's eligible keys, S_U loads in flight per thread
+  auto each_key = [&](auto&& f) {
+    for (int64_t b = c0 + tid; b < c1; b += (int64_t)SNT * S_U) {
+      uint64_t v[S_U];
+#pragma unroll
+      for (int u = 0; u < S_U; ++u) {
+        const int64_t j = b + (int64_t)u * SNT;
+        v[u] = j < c1 ? keys[j] : 0ull;
+      }
+#pragma unroll
+      for (int u = 0; u < S_U; ++u)
+        if (v[u] != 0ull) f(v[u]);
+    }
+  };
+  if (tid < 6) s_misc[tid] = 0;
+  __syncthreads();
+  // A list that fits the stage is read from global memory once: the first pass copies it
+  // to LDS as it stands (ineligible zeros included; every LDS pass skips them).
+  const bool small = c1 - c0 <= (int64_t)S_STAGE;
+  // first pass: eligible count, smallest and largest key
+  {
+    uint32_t nz = 0;
+    uint64_t mn = ~0ull, mx = 0ull;
+    if (small) {
+      for (int64_t b = c0 + tid; b < c1; b += (int64_t)SNT * S_U) {
+        uint64_t v[S_U];
+#pragma unroll
+        for (int u = 0; u < S_U; ++u) {
+          const int64_t j = b + (int64_t)u * SNT;
+          v[u] = j < c1 ? keys[j] : 0ull;
+        }
+#pragma unroll
+        for (int u = 0; u < S_U; ++u) {
+          const int64_t j = b + (int64_t)u * SNT;
+          if (j < c1) c_key[j - c0] = v[u];
+          if (v[u] != 0ull) {
+            ++nz;
+            mn = v[u] < mn ? v[u] : mn;
+            mx = v[u] > mx ? v[u] : mx;
+          }
+        }
+      }
+    } else {
+      each_key([&](uint64_t key) {
+        ++nz;
+        mn = key < mn ? key : mn;
+        mx = key > mx ? key : mx;
+      });
+    }
+    mn = wave_min_u64(mn);
+    mx = wave_max_u64(mx);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nz += __shfl_xor(nz, o, 64);
+    if (lane == 0) {
+      s_mn[wave] = mn;
+      s_mx[wave] = mx;
+      if (nz) atomicAdd(&s_misc[0], nz);
+    }
+  }
+  __syncthreads();
+  const uint32_t M = s_misc[0];
+  const int cnt = (int)(M < (uint32_t)k ? M : (uint32_t)k);
+  uint64_t kth = 0;  // keep every eligible key
+  // staged: c_key[0 .. ns) holds every key that matched the prefix when it was filled
+  // (zeros to skip), and the keys above that prefix -- winners for sure -- are in s_key
+  bool staged = small;
+  uint32_t ns = small ? (uint32_t)(c1 - c0) : 0u;
+  // distinct keys: exactly cnt winners (the slot test only guards the outputs against a
+  // list that broke the unique-id contract)
+  auto take = [&](uint64_t key) {
+    const uint32_t slot = atomicAdd(&s_misc[3], 1u);
+    if (slot < (uint32_t)cnt) s_key[slot] = key;
+  };
+  if (M > (uint32_t)k) {
+    uint64_t mn = s_mn[0], mx = s_mx[0];
+    for (int w = 1; w < SNT / 64; ++w) {
+      mn = s_mn[w] < mn ? s_mn[w] : mn;
+      mx = s_mx[w] > mx ? s_mx[w] : mx;
+    }
+    // 8-bit digits from the highest bit where the keys differ (distinct keys: mn != mx)
+    int hi = 63 - __builtin_clzll((mn ^ mx) | 1ull);
+    uint64_t pmask = hi >= 63 ? 0ull : (~0ull << (hi + 1));
+    uint64_t prefix = mn & pmask;
+    uint32_t kr = (uint32_t)k;
+    uint32_t nsel = M;
+    for (;;) {
+      const int lo = hi >= 7 ? hi - 7 : 0;
+      const uint32_t dm = (2u << (hi - lo)) - 1u;
+      bool fill = false;
+      if (!staged && nsel <= (uint32_t)S_STAGE) {
+        // the selected bucket fits: the last pass over global memory moves it to LDS and
+        // collects the keys above it
+        each_key([&](uint64_t key) {
+          const uint64_t kp = key & pmask;
+          if (kp == prefix) {
+            const uint32_t slot = atomicAdd(&s_misc[5], 1u);
+            if (slot < (uint32_t)S_STAGE) c_key[slot] = key;
+          } else if (kp > prefix) {
+            take(key);
+          }
+        });
+        staged = fill = true;
+      }
+      for (int j = tid; j < S_NH * 256; j += SNT) (&hist[0][0])[j] = 0;
+      __syncthreads();
+      if (fill) ns = s_misc[5] < (uint32_t)S_STAGE ? s_misc[5] : (uint32_t)S_STAGE;
+      uint32_t* hw = hist[wave & (S_NH - 1)];
+      if (staged) {
+        for (uint32_t j = tid; j < ns; j += SNT) {
+          const uint64_t key = c_key[j];
+          if (key != 0ull && (key & pmask) == prefix)
+            atomicAdd(&hw[(uint32_t)(key >> lo) & dm], 1u);
+        }
+      } else {
+        each_key([&](uint64_t key) {
+          if ((key & pmask) == prefix) atomicAdd(&hw[(uint32_t)(key >> lo) & dm], 1u);
+        });
+      }
+      __syncthreads();
+      if (wave == 0) {
+        uint32_t bb[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          uint32_t t = 0;
+#pragma unroll
+          for (int w = 0; w < S_NH; ++w) t += hist[w][4 * lane + j];
+          bb[j] = t;
+        }
+        const uint32_t c4 = bb[0] + bb[1] + bb[2] + bb[3];
+        uint32_t suf = c4;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const uint32_t t = __shfl_down(suf, o, 64);
+          if (lane + o < 64) suf += t;
+        }
+        const uint32_t above = suf - c4;
+        if (suf >= kr && above < kr) {
+          uint32_t acc = above;
+          int sel = 4 * lane;
+          uint32_t bsz = bb[0];
+          for (int j = 3; j >= 0; --j) {
+            if (acc + bb[j] >= kr) {
+              sel = 4 * lane + j;
+              bsz = bb[j];
+              break;
+            }
+            acc += bb[j];
+          }
+          s_misc[2] = (uint32_t)sel;
+          s_misc[1] = kr - acc;
+          s_misc[4] = bsz;
+        }
+      }
+      __syncthreads();
+      prefix |= (uint64_t)s_misc[2] << lo;
+      pmask |= (uint64_t)dm << lo;
+      kr = s_misc[1];
+      nsel = s_misc[4];
+      __syncthreads();  // s_misc and hist are rewritten by the next pass
+      // the bucket holds exactly the keys still wanted: every key >= its lowest possible
+      // member wins
+      if (nsel == kr || lo == 0) break;
+      hi = lo - 1;
+    }
+    kth = prefix;
+  }
+  // the winners: every key >= kth (those above the staged bucket are collected already)
+  if (staged) {
+    for (uint32_t j = tid; j < ns; j += SNT) {
+      const uint64_t key = c_key[j];
+      if (key != 0ull && key >= kth) take(key);
+    }
+  } else {
+    each_key([&](uint64_t key) {
+      if (key >= kth) take(key);
+    });
+  }
+  __syncthreads();
+  int npow = 1;
+  while (npow < cnt) npow <<= 1;
+  {
+    uint32_t filled = s_misc[3];
+    filled = filled < (uint32_t)cnt ? filled : (uint32_t)cnt;
+    for (int j = (int)filled + tid; j < npow; j += SNT) s_key[j] = 0ull;
+  }
+  __syncthreads();
+  for (int size = 2; size <= npow; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      const int j = tid ^ stride;
+      if (tid < npow && j > tid) {
+        const bool desc = (tid & size) == 0;
+        const uint64_t a = s_key[tid], b = s_key[j];
+        if (desc ? (a < b) : (a > b)) {
+          s_key[tid] = b;
+          s_key[j] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int j = tid; j < k; j += SNT) {
+    float sc = -__builtin_huge_valf();
+    int64_t id = -1;
+    const uint64_t key = j < cnt ? s_key[j] : 0ull;
+    if (key != 0ull) {
+      sc = unorderable_f32((uint32_t)(key >> 32));
+      id = (int64_t)(uint32_t)(~(uint32_t)key);
+    }
+    out_score[q * k + j] = sc;
+    out_idx[q * k + j] = id;
+  }
+  if (tid == 0) out_n[q] = cnt;
+}
+
+static bool supported_d(int64_t D) {  // the scan's set (scan_topk.hip)
+  return D == 64 || D == 128 || D == 256 || D == 384 || D == 512 || D == 768 || D == 1024;
+}
+
+static size_t workspace_bytes_for(int64_t n_cand) {
+  const size_t keys = (size_t)(n_cand > 0 ? n_cand : 0) * 8;
+  return ((keys + 255) & ~(size_t)255) + 256;
+}
+
+}  // namespace rerank
+}  // namespace irc
+
+using namespace irc;
+using namespace irc::rerank;
+
+extern "C" int irc_rerank_chunk(void) { return RR_CHUNK; }
+
+extern "C" int64_t irc_rerank_topk_workspace(int64_t Q, int64_t n_cand, int64_t k) {
+  (void)Q;
+  (void)k;
+  return (int64_t)workspace_bytes_for(n_cand);
+}
+
+extern "C" int irc_rerank_topk(const void* queries, const void* docs, int64_t Q, int64_t N,
+                               int64_t D, const int32_t* cand, const int64_t* cand_off,
+                               int64_t n_cand, int64_t k, int64_t doc_offset, void* workspace,
+                               int64_t workspace_bytes, float* out_score, int64_t* out_idx,
+                               int32_t* out_n, irc_stream_t stream) {
+  IRC_REQUIRE(Q >= 0 && N >= 0 && n_cand >= 0, "rerank_topk: negative size");
+  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "rerank_topk: k=%lld outside [1, %d]", (long long)k,
+              RR_MAXK);
+  IRC_REQUIRE(supported_d(D), "rerank_topk: unsupported D=%lld", (long long)D);
+  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
+              "rerank_topk: global doc ids must fit int32 (doc_offset + N < 2^31)");
+  IRC_REQUIRE(Q < (1ll << 31) - 1, "rerank_topk: Q too large");
+  IRC_REQUIRE(n_cand < (1ll << 31) * RR_CHUNK, "rerank_topk: n_cand too large");
+  if (workspace == nullptr || workspace_bytes < (int64_t)workspace_bytes_for(n_cand)) {
+    set_error("rerank_topk: workspace %lld < required %lld bytes", (long long)workspace_bytes,
+              (long long)workspace_bytes_for(n_cand));
+    return IRC_E_WORKSPACE;
+  }
+  if (Q == 0) return IRC_OK;
+  IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n, "rerank_topk: null pointer");
+  IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)), "rerank_topk: null candidates / docs");
+  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
+              "rerank_topk: queries and docs must be 16-byte aligned");
+  hipStream_t st = as_stream(stream);
+  uint64_t* keys = static_cast<uint64_t*>(workspace);
+  if (n_cand > 0) {
+    const unsigned blocks = (unsigned)((n_cand + RR_CHUNK - 1) / RR_CHUNK);
+    const unsigned short* qp = static_cast<const unsigned short*>(queries);
+    const unsigned short* dp = static_cast<const unsigned short*>(docs);
+    prof_begin(st);
+#define IRC_RR_CASE(DD)                                                                      \
+  case DD:                                                                                   \
+    hipLaunchKernelGGL((rerank_score_kernel<DD>), dim3(blocks), dim3(RR_CHUNK), 0, st, qp, dp, \
+                       (int)Q, N, cand, cand_off, n_cand, doc_offset, keys);                 \
+    break;
+    switch (D) {
+      IRC_RR_CASE(64)
+      IRC_RR_CASE(128)
+      IRC_RR_CASE(256)
+      IRC_RR_CASE(384)
+      IRC_RR_CASE(512)
+      IRC_RR_CASE(768)
+      default: IRC_RR_CASE(1024)
+    }
+#undef IRC_RR_CASE
+    prof_end("rerank_score", st, (double)n_cand * D * 2.0);  // the gathered row bytes
+    if (int rc = check_launch("rerank_score_kernel")) return rc;
+  }
+  prof_begin(st);
+  hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)Q), dim3(SNT), 0, st, keys, cand_off,
+                     n_cand, (int)k, out_score, out_idx, out_n);
+  prof_end("rerank_select", st, (double)n_cand * 8.0);
+  return check_launch("rerank_select_kernel");
+}

@@ -171,6 +171,76 @@ def topk_merge(scores: torch.Tensor, idx: torch.Tensor, k: int):
     return out_s, out_i
 
 
+def __getattr__(name):
+    # RERANK_CHUNK: the candidates one scoring workgroup of irc_rerank_topk takes, read from
+    # the library (irc_rerank_chunk(), RR_CHUNK in csrc/rerank.hip) so it cannot drift; the
+    # list lengths around it are the kernel's edge cases.
+    if name == "RERANK_CHUNK":
+        return int(_lib.load().irc_rerank_chunk())
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def rerank_topk(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
+                cand_off: torch.Tensor, k: int, doc_offset: int = 0, ws_tag: str = "rerank"):
+    """Exact top-k of each query over ITS OWN candidate docs (sparse filter, dense rerank:
+    src/evaluation.py:57-83 feeding :110-112).
+
+    queries [Q, D], docs [N, D] (one shard, first global id ``doc_offset``), bf16 on one
+    HIP device.  ``cand`` (int32 or int64) holds global doc ids, query q owning
+    ``cand[cand_off[q]:cand_off[q + 1]]`` (``cand_off`` int64 [Q + 1]); ids are unique
+    within a list, in any order; ids outside the shard are skipped (an int64 id that does
+    not fit int32 is in no shard and is skipped too, never wrapped).  Returns (scores fp32
+    [Q, k], idx int64 [Q, k], n int32 [Q]): each list by (score desc, id asc), slots past
+    n[q] = min(k, eligible) are (-inf, -1)."""
+    require_hip(queries, docs, cand, cand_off)
+    q = contig(queries, torch.bfloat16)
+    d = contig(docs, torch.bfloat16)
+    Q, D = q.shape
+    N = d.shape[0]
+    if d.shape[1] != D:
+        raise ValueError(f"dim mismatch: queries D={D}, docs D={d.shape[1]}")
+    if cand.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"cand must be int32 or int64, not {cand.dtype}")
+    if cand_off.numel() != Q + 1:
+        raise ValueError(f"cand_off has {cand_off.numel()} entries for {Q} queries (Q + 1)")
+    if cand.dtype == torch.int64:
+        # an id outside int32 is in no shard (doc_offset + N < 2^31): it must not wrap into one
+        cand = torch.where((cand < 0) | (cand >= 2 ** 31), cand.new_full((), -1), cand)
+    c = contig(cand, torch.int32)
+    off = contig(cand_off, torch.int64)
+    n_cand = c.numel()
+    out_s = torch.empty((Q, k), dtype=torch.float32, device=q.device)
+    out_i = torch.empty((Q, k), dtype=torch.int64, device=q.device)
+    out_n = torch.empty((Q,), dtype=torch.int32, device=q.device)
+    nbytes = int(_lib.fn("irc_rerank_topk_workspace")(Q, n_cand, k))
+    ws = workspace(nbytes, q.device, ws_tag)
+    _lib.call("irc_rerank_topk", ptr(q), ptr(d), Q, N, D, ptr(c), ptr(off), n_cand, k,
+              doc_offset, ptr(ws), ws.numel(), ptr(out_s), ptr(out_i), ptr(out_n),
+              stream_ptr(q.device))
+    return out_s, out_i, out_n
+
+
+def expand_ranges(cand: torch.Tensor, cand_off: torch.Tensor, row_off: torch.Tensor):
+    """Candidate columns -> candidate rows: each candidate c of the CSR pair (cand,
+    cand_off) becomes the row range [row_off[c], row_off[c + 1]) (empty ranges vanish) and
+    the offsets are rebuilt.  Returns (rows int64, rows_off int64 [Q + 1]); lists that
+    were ascending and unique stay so (row_off is non-decreasing).  Pure torch on the
+    tensors' device; the one host synchronisation is the total row count."""
+    c = cand.to(torch.int64)
+    off = cand_off.to(torch.int64)
+    ro = row_off.to(device=c.device, dtype=torch.int64)
+    start = ro[c]
+    length = ro[c + 1] - start
+    ends = torch.cumsum(length, 0)  # flat end of every candidate's rows
+    zero = torch.zeros(1, dtype=torch.int64, device=c.device)
+    rows_off = torch.cat([zero, ends])[off]
+    total = int(ends[-1].item()) if c.numel() else 0
+    owner = torch.repeat_interleave(torch.arange(c.numel(), device=c.device), length,
+                                    output_size=total)
+    rows = start[owner] + (torch.arange(total, device=c.device) - (ends - length)[owner])
+    return rows, rows_off
+
+
 def shard_bounds(n_docs: int, world: int, rank: int):
     """Contiguous shard [start, stop) of rank `rank` (first n % world ranks get +1)."""
     base, rem = divmod(n_docs, world)
@@ -275,6 +345,41 @@ class ShardedDenseIndex:
         allq = self._gather_queries(queries, equal_counts)  # (1)
         s, i = self._local_topk(allq, k, ws_tag)  # (2)
         return self._exchange_merge(s, i, k)  # (3)
+
+    def search_candidates(self, queries: torch.Tensor, cand: torch.Tensor,
+                          cand_off: torch.Tensor, k: int, ws_tag: str = "rerank"):
+        """Top-k of each query over its own candidate docs only (global ids, the CSR pair
+        ``SparseIndex.candidates`` / ``expand_ranges`` leave on the device): (scores
+        [Q, k], idx [Q, k], n [Q]) as ``rerank_topk``.  bf16 shards, single process.
+
+        Cost model: the candidate rows are gathered whole, once per
+        (query, candidate), with no reuse across queries -- n_cand * D * 2 bytes -- while
+        ``search`` streams the shard once for the whole batch.  So this call wins while
+        the lists are sparse and loses once they are dense; it is the only one of the two
+        that ranks the candidates alone.
+
+        Measured (tools/rerank_probe.py, profiles/rerank_probe.json: one MI355X, 250k x 768
+        shard, random lists redrawn call by call, k = 100; call times in us, this call /
+        ``search``; ``tools/rerank_probe.py --tables`` prints this from the file):
+
+            candidates per query     Q = 1         Q = 16        Q = 64        Q = 256
+                 250 (0.1 %)         20 / 80       25 / 84       27 / 95        32 / 165
+               2,500 (1 %)           26 / 80       30 / 84       55 / 94       158 / 164
+              12,500 (5 %)           36 / 80       74 / 84      200 / 94       691 / 164
+              62,500 (25 %)          74 / 80      271 / 84      876 / 94     3,303 / 164
+
+        The two cross at about 1.0 % of the shard per query at Q = 256, 2.0 % at Q = 64,
+        5.8 % at Q = 16, and above 25 % at Q = 1.  The scoring pass gathers 4.8-7.6 TB/s of
+        row bytes from 160k candidates up (lists of one call that overlap hit the caches)
+        and is latency-bound below."""
+        if self.dtype == "fp8":
+            raise ValueError("search_candidates scores bf16 shards only (dtype='fp8' index)")
+        if self._sharded():
+            raise NotImplementedError(
+                "search_candidates over a process group: the all_gather of the queries and "
+                "candidate lists and of the per-shard top-k lists (search()'s collectives) "
+                "is not built; the per-shard rerank_topk call already skips foreign ids")
+        return rerank_topk(queries, self.docs, cand, cand_off, k, self.doc_offset, ws_tag=ws_tag)
 
     # The three steps of a sharded search, separately callable (bench.py times each).
     def _sharded(self):

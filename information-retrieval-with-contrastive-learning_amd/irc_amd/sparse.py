@@ -174,16 +174,26 @@ class SparseIndex:
                   ptr(out_off), ptr(out), st)
         return out[:total], out_off
 
-    def documents_filtering(self, claims, bigram_only: bool = True):
-        """src/evaluation.py:57-81 for a batch of claims: per claim the sorted doc
-        indices sharing a hashed n-gram (bigrams only when bigram_only)."""
+    def _claim_rows(self, claims, bigram_only: bool):
+        """Per claim the unique hashed n-gram rows (src/evaluation.py:57-70)."""
         row_lists = []
         for c in claims:
             grams = ngrams(tokenize(c), self.ngram)
             if bigram_only:
                 grams = [g for g in grams if len(g.split()) > 1]
             row_lists.append(np.unique([feature_hash(g, self.hash_size) for g in grams]))
-        idx, off = self.union(row_lists)
+        return row_lists
+
+    def candidates(self, claims, bigram_only: bool = True):
+        """documents_filtering's candidates left on the device: (idx int32, off int64
+        [len(claims) + 1]), claim i owning idx[off[i]:off[i + 1]], ascending and unique
+        -- the input of ShardedDenseIndex.search_candidates, no host copy."""
+        return self.union(self._claim_rows(claims, bigram_only))
+
+    def documents_filtering(self, claims, bigram_only: bool = True):
+        """src/evaluation.py:57-81 for a batch of claims: per claim the sorted doc
+        indices sharing a hashed n-gram (bigrams only when bigram_only)."""
+        idx, off = self.candidates(claims, bigram_only)
         idx, off = idx.cpu().numpy(), off.cpu().numpy()
         return [idx[off[i]:off[i + 1]].astype(np.int64) for i in range(len(claims))]
 

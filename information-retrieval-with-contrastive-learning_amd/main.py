@@ -2,7 +2,7 @@
 
     python main.py [--config config.yaml] [--data doc|fever] [--gpu 0] [--ckpt X]
                    [--model LSTM|BERT] [--loss InfoNCE] [--opt adam] [--sample uniform|tf_idf]
-                   [--seed 1337] [--logdir log] [--ckptdir ckpt] [--retrieval sparse|dense]
+                   [--seed 1337] [--logdir log] [--ckptdir ckpt] [--retrieval sparse|dense|hybrid]
 
 Multi-GPU (one process per GPU):
     torchrun --nproc-per-node N --master-addr 127.0.0.1 main.py [same flags]
@@ -15,7 +15,9 @@ shards the evidence corpus over the ranks.  IRC_DIST_BACKEND=gloo selects gloo
 
 --data doc trains (src.train.train); --data fever runs src.evaluation.predict:
 the reference's sparse candidate filter per claim (default) or, with
-``--retrieval dense``, the bi-encoder's exact top-k over the evidence corpus.  The compute runs on the MI355X HIP kernels only:
+``--retrieval dense``, the bi-encoder's exact top-k over the evidence corpus, or, with
+``--retrieval hybrid``, that top-k over each claim's filter candidates only (the
+reference's two stages joined; single process).  The compute runs on the MI355X HIP kernels only:
 ``--gpu -1`` (CPU) is rejected -- there is no CPU fallback in this build.
 """
 import argparse
@@ -51,9 +53,11 @@ def get_args(argv=None):
                    choices=["InfoNCE", "ProtoNCE", "HProtoNCE"])
     p.add_argument("--opt", default="adam", type=str, choices=["adam", "sgd"])
     p.add_argument("--sample", default="uniform", type=str, choices=["uniform", "tf_idf"])
-    p.add_argument("--retrieval", default="sparse", type=str, choices=["sparse", "dense"],
-                   help="--data fever: sparse n-gram filter as the reference (default) or "
-                        "dense bi-encoder top-k (superset)")
+    p.add_argument("--retrieval", default="sparse", type=str,
+                   choices=["sparse", "dense", "hybrid"],
+                   help="--data fever: sparse n-gram filter as the reference (default), "
+                        "dense bi-encoder top-k (superset), or hybrid: the filter's "
+                        "candidates reranked by the bi-encoder (the reference's two stages)")
     return p.parse_args(argv)
 
 

@@ -9,7 +9,10 @@ sketches in its commented-out tail (:110-115): ``ctx2vec`` embeddings
 (contrastive_module.py:96-100) of the evidence corpus sharded into HBM and each
 claim batch scored against all of them with the exact top-k scan
 (irc_amd.retrieval, closest_docs ordering, tfidf_doc_ranker.py:60-75), then
-evidence recall@k printed.
+evidence recall@k printed.  ``--retrieval hybrid`` joins the two as the reference's
+predict() describes: the filter's candidates (:57-83) stay on the device and the
+dense scores (:110-112) rank each claim's candidates only (``hybrid_search``,
+irc_rerank_topk).
 """
 import pickle
 import time
@@ -69,6 +72,8 @@ def predict(args, k=100):
     predict_dense.  Returns the per-claim candidate counts (sparse) or recall@k."""
     if getattr(args, "retrieval", "sparse") == "dense":
         return predict_dense(args, k)
+    if getattr(args, "retrieval", "sparse") == "hybrid":
+        return predict_hybrid(args, k)
     assert args.ckpt is not None
     _, model, _, _ = load_model(args.ckpt)
     model = model.to(args.device)
@@ -142,4 +147,75 @@ def predict_dense(args, k=100):
             total += 1
     if rank == 0:
         print(f"evidence recall@{k}: {hits / max(total, 1):.4f}")
+    return hits / max(total, 1)
+
+
+def hybrid_corpus(wiki, doc_ids):
+    """The dense corpus of the two-stage pipeline, in count-matrix column order: column
+    i is the page ``doc_ids[i]`` (metadata["doc_dict"][1]); if the wiki has it, its
+    non-empty lines become rows.  Returns (titles, texts, row_off): one title and text
+    per row, and row_off [n_cols + 1] with column i owning rows [row_off[i],
+    row_off[i + 1]) -- empty for a column absent from the wiki."""
+    titles, texts, row_off = [], [], [0]
+    for doc_id in doc_ids:
+        page = wiki.get(doc_id)
+        if page is not None:
+            for line in page["lines"]:
+                if line.strip():
+                    titles.append(doc_id)
+                    texts.append(line)
+        row_off.append(len(texts))
+    return titles, texts, row_off
+
+
+@torch.no_grad()
+def hybrid_search(model, dense_index, sparse_index, row_off, claims, k, device,
+                  bigram_only=False):
+    """Sparse filter, dense rerank for a batch of claims (src/evaluation.py:57-83 feeding
+    :110-112), all on the device: the claims' candidate columns (SparseIndex.candidates)
+    expanded to their evidence rows (``row_off``, int64 [n_cols + 1] on the device) and
+    each claim's ``ctx2vec`` embedding ranked against its own rows only.  Returns
+    (scores [Q, k], idx [Q, k] corpus rows, n [Q]) as rerank_topk."""
+    from irc_amd.retrieval import expand_ranges
+
+    q = model.ctx2vec(claims, device)
+    cand, off = sparse_index.candidates(claims, bigram_only)
+    rows, rows_off = expand_ranges(cand, off, row_off)
+    return dense_index.search_candidates(q, rows, rows_off, k)
+
+
+@torch.no_grad()
+def predict_hybrid(args, k=100):
+    """The reference's two-stage predict: per claim batch the hashed n-gram filter, then
+    the bi-encoder's exact top-k over the filter's candidates only.  Prints each batch's
+    latency and the evidence recall@k (a claim with no candidates is a miss); returns
+    recall@k.  Single process."""
+    assert args.ckpt is not None
+    if getattr(args, "dist_group", None) is not None and int(getattr(args, "world_size", 1)) > 1:
+        raise NotImplementedError("--retrieval hybrid runs in a single process: the collective "
+                                  "around search_candidates is not built")
+    _, model, _, _ = load_model(args.ckpt)
+    model = model.to(args.device).eval()
+    loader = get_dataloader(args, train=False, distributed=False)
+    ds = args.config["dataset"]
+    _, metadata = load_sparse_csr(ds["tfidf"])
+    count_matrix, _ = load_sparse_csr(ds["inverted_file"])
+    if metadata.get("tokenizer", "simple") != "simple":
+        raise ValueError("only the DrQA 'simple' tokenizer is supported on this path")
+    sparse_index = SparseIndex(count_matrix, ngram=metadata["ngram"], device=args.device)
+    titles, texts, row_off = hybrid_corpus(loader.dataset.wiki, metadata["doc_dict"][1])
+    row_off = torch.tensor(row_off, dtype=torch.int64, device=args.device)
+    index = ShardedDenseIndex(encode_corpus(model, texts, args.device))
+    hits = total = 0
+    for batch in tqdm(loader, desc="Iteration"):
+        claims = [d["claim"] for d in batch]
+        s = time.time()
+        _, idx, _ = hybrid_search(model, index, sparse_index, row_off, claims, k, args.device)
+        torch.cuda.synchronize()
+        print(f"batch of {len(claims)} claims: {time.time() - s:.4f}s")
+        for d, row in zip(batch, idx.cpu().tolist()):
+            gold = {e["title"] for e in d["evidences"]}
+            hits += int(any(titles[j] in gold for j in row if j >= 0))
+            total += 1
+    print(f"evidence recall@{k}: {hits / max(total, 1):.4f}")
     return hits / max(total, 1)

@@ -1,0 +1,193 @@
+"""Candidate-restricted top-k against the full scan: where the two cross.
+
+    python tools/rerank_probe.py [--n 250000] [--d 768] [--k 100] [--rounds 10] [--sets 4]
+    python tools/rerank_probe.py --tables profiles/rerank_probe.json   # the documents' tables
+
+One MI355X, the C3 shard (250k x 768 bf16, larger than the Infinity Cache), random
+ascending candidate lists of 0.1 / 1 / 5 / 25 % of the shard per query, Q in {1, 16, 64,
+256}.  Per cell: the rerank call (retrieval.rerank_topk) and the scan call
+(retrieval.scan_topk, same Q, same shard) timed with HIP events around windows of
+back-to-back calls (100 ms of work each), the two alternating round by round in one
+process (median over the rounds); the rerank calls of a window cycle through `sets`
+independent draws of the lists, as a serving loop's batches would bring new lists; then, in a separate profiled pass, the scoring and select kernels' own times
+(the library's per-launch events) and the scoring pass's achieved bytes/s, n_cand * D * 2
+over its time, beside the 5.5-5.8 TB/s whole-row gather rate of 1,152-2,304-byte rows.
+Prints a table to stderr and ONE JSON line to stdout."""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "information-retrieval-with-contrastive-learning_amd"))
+
+import torch  # noqa: E402
+
+GATHER_TBS = (5.5, 5.8)  # whole-row gather, 1,152-2,304-B rows
+
+
+def _window_ms(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def _prof(lib, name):
+    tot, cnt, work = ctypes.c_double(0), ctypes.c_int64(0), ctypes.c_double(0)
+    lib.irc_prof_query(name, ctypes.byref(tot), ctypes.byref(cnt), ctypes.byref(work))
+    n = max(cnt.value, 1)
+    return tot.value * 1e3 / n, work.value / n  # us per launch, work per launch
+
+
+def tables(path):
+    """The tables of DESIGN.md 6e and of the search_candidates docstring, from a recorded
+    JSON line (no device needed): what the documents quote is what the file holds."""
+    with open(path) as f:
+        r = json.load(f)
+    cells = r["cells"]
+    print("| Q | candidates / query | rerank call | scoring kernel | scoring TB/s | "
+          "select kernel | scan call |\n|---|---|---|---|---|---|---|")
+    for c in cells:
+        print(f"| {c['Q']} | {c['cand_per_query']:,} ({100 * c['frac']:g}%) | "
+              f"{c['rerank_call_us']:,.1f} | {c['score_kernel_us']:,.1f} | "
+              f"{c['score_TBps']:.2f} | {c['select_kernel_us']:.1f} | {c['scan_call_us']:.1f} |")
+    print()
+    qs = sorted({c["Q"] for c in cells})
+    print("    candidates per query  " + "".join(f"{'Q = ' + str(q):>16}" for q in qs))
+    for frac in sorted({c["frac"] for c in cells}):
+        row = {c["Q"]: c for c in cells if c["frac"] == frac}
+        n = next(iter(row.values()))["cand_per_query"]
+        print(f"    {n:>8,} ({100 * frac:g} %)".ljust(26) + "".join(
+            f"{row[q]['rerank_call_us']:>9,.0f} / {row[q]['scan_call_us']:<4.0f}" for q in qs))
+    print()
+    print("crossover:", r["crossover_frac"])
+    for m in ("rerank", "scan"):
+        worst = max(cells, key=lambda c: c["spread_pct"][m])
+        print(f"largest min-max spread of the {m} windows: {worst['spread_pct'][m]:.2f}% "
+              f"(Q = {worst['Q']}, {100 * worst['frac']:g}%)")
+    big = [c for c in cells if c["n_cand"] >= 160000]
+    print(f"scoring TB/s at n_cand >= 160k: {min(c['score_TBps'] for c in big):.2f}-"
+          f"{max(c['score_TBps'] for c in big):.2f}")
+    longest = [c for c in cells if c["cand_per_query"] == max(x["cand_per_query"] for x in cells)]
+    print(f"select kernel at {longest[0]['cand_per_query']:,} keys: "
+          f"{min(c['select_kernel_us'] for c in longest):.1f}-"
+          f"{max(c['select_kernel_us'] for c in longest):.1f} us")
+
+
+def main():
+    if len(sys.argv) == 3 and sys.argv[1] == "--tables":
+        return tables(sys.argv[2])
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=250_000)
+    ap.add_argument("--d", type=int, default=768)
+    ap.add_argument("--k", type=int, default=100)
+    ap.add_argument("--rounds", type=int, default=10)
+    ap.add_argument("--window-ms", type=float, default=100.0, help="timed work per window")
+    ap.add_argument("--sets", type=int, default=4,
+                    help="independent candidate draws per cell, cycled call by call")
+    ap.add_argument("--q", type=int, nargs="*", default=[1, 16, 64, 256])
+    ap.add_argument("--frac", type=float, nargs="*", default=[0.001, 0.01, 0.05, 0.25])
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("rerank_probe measures on a HIP device; none is visible")
+    from irc_amd import _lib, retrieval
+
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(2025)
+    docs = torch.nn.functional.normalize(
+        torch.randn(args.n, args.d, generator=g)).bfloat16().to(dev)
+    torch.manual_seed(2025)
+    cells = []
+    for Q in args.q:
+        qq = torch.nn.functional.normalize(
+            torch.randn(Q, args.d, generator=g)).bfloat16().to(dev)
+        scan = lambda: retrieval.scan_topk(qq, docs, args.k)  # noqa: E731
+        for frac in args.frac:
+            n = max(1, int(round(frac * args.n)))
+            # a serving loop brings new lists with every batch: the calls of a window cycle
+            # through `sets` independent draws, so a call does not find its own rows of the
+            # call before in the Infinity Cache (4 draws of 5% x 16 queries already cover
+            # nearly the whole 384 MB shard)
+            cands = [torch.cat([torch.randperm(args.n, device=dev)[:n].sort().values
+                                for _ in range(Q)]).to(torch.int32) for _ in range(args.sets)]
+            off = torch.arange(Q + 1, device=dev, dtype=torch.int64) * n
+            turn = [0]
+
+            def rer():
+                turn[0] += 1
+                return retrieval.rerank_topk(qq, docs, cands[turn[0] % args.sets], off, args.k)
+
+            est = {}
+            for name, fn in (("rerank", rer), ("scan", scan)):
+                for _ in range(3):
+                    fn()
+                torch.cuda.synchronize()
+                est[name] = _window_ms(fn, 5)
+            reps = {m: max(2 * args.sets, min(4000, int(args.window_ms / max(est[m], 1e-3))))
+                    for m in est}
+            reps["rerank"] -= reps["rerank"] % args.sets  # every draw equally often
+            t = {"rerank": [], "scan": []}
+            for _ in range(args.rounds):  # alternate the two
+                t["rerank"].append(_window_ms(rer, reps["rerank"]))
+                t["scan"].append(_window_ms(scan, reps["scan"]))
+            # kernel times in a pass of their own (per-launch events slow the host)
+            lib.irc_prof_reset()
+            lib.irc_prof_enable(1)
+            for _ in range(min(reps["rerank"], 12 * args.sets)):
+                rer()
+            torch.cuda.synchronize()
+            lib.irc_prof_enable(0)
+            score_us, score_bytes = _prof(lib, b"rerank_score")
+            select_us, _ = _prof(lib, b"rerank_select")
+            cell = {
+                "Q": Q, "frac": frac, "cand_per_query": n, "n_cand": Q * n,
+                "rerank_call_us": statistics.median(t["rerank"]) * 1e3,
+                "rerank_call_us_minmax": [min(t["rerank"]) * 1e3, max(t["rerank"]) * 1e3],
+                "scan_call_us": statistics.median(t["scan"]) * 1e3,
+                "scan_call_us_minmax": [min(t["scan"]) * 1e3, max(t["scan"]) * 1e3],
+                "score_kernel_us": score_us, "select_kernel_us": select_us,
+                "score_bytes": score_bytes,
+                "score_TBps": score_bytes / (score_us * 1e-6) / 1e12 if score_us else None,
+                "reps": reps,
+                "spread_pct": {m: 100.0 * (max(t[m]) - min(t[m])) / statistics.median(t[m])
+                               for m in t},
+            }
+            cells.append(cell)
+            print(f"Q={Q:4d} frac={frac:6.3f} n_cand={Q * n:9d}  rerank {cell['rerank_call_us']:9.1f} us"
+                  f"  (score {score_us:9.1f} us, {cell['score_TBps'] or 0:5.2f} TB/s; select "
+                  f"{select_us:7.1f} us)  scan {cell['scan_call_us']:8.1f} us", file=sys.stderr,
+                  flush=True)
+    # candidate fraction where the two call times cross, per Q: log-log interpolation
+    # between the two measured fractions that bracket it
+    import math
+
+    cross = {}
+    for Q in args.q:
+        row = sorted((c for c in cells if c["Q"] == Q), key=lambda c: c["frac"])
+        r = [math.log(c["rerank_call_us"] / c["scan_call_us"]) for c in row]
+        val = None
+        if r and r[0] > 0:
+            val = f"< {row[0]['frac']}"
+        elif r and r[-1] < 0:
+            val = f"> {row[-1]['frac']}"
+        for a, b, ra, rb in zip(row, row[1:], r, r[1:]):
+            if ra <= 0 < rb:
+                w = -ra / (rb - ra)
+                val = math.exp(math.log(a["frac"]) + w * (math.log(b["frac"]) - math.log(a["frac"])))
+        cross[str(Q)] = val
+    print(json.dumps({"probe": "rerank_vs_scan", "device": torch.cuda.get_device_name(0),
+                      "N": args.n, "D": args.d, "k": args.k, "rounds": args.rounds,
+                      "window_ms": args.window_ms, "sets": args.sets,
+                      "gather_guide_TBps": list(GATHER_TBS), "cells": cells,
+                      "crossover_frac": cross}))
+
+
+if __name__ == "__main__":
+    main()
