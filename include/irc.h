@@ -34,6 +34,9 @@ typedef void* irc_stream_t; /* hipStream_t */
 #define IRC_E_LAUNCH 1003    /* kernel launch failed */
 
 const char* irc_last_error(void);
+/* Bumped whenever an entry point goes or an argument changes meaning.
+ * 2: only a negative max_blocks of irc_gemm_ex is a grid cap; a positive one caps the
+ *    split-K launch and no longer the grid of an unsplit launch. */
 int irc_abi_version(void);
 
 /* ------------------------------------------------------------------ retrieval
@@ -193,14 +196,12 @@ int64_t irc_gemm_workspace_ex(int in_dtype, int out_dtype, int epilogue, int64_t
  * default); 1 = each workgroup takes tiles from a tile counter and DMAs the next
  * tile's first K-tile while this tile's epilogue runs; 2 = static waves of tiles
  * with that prestage; 3 = static waves without it.  Same arithmetic per tile, so
- * the results are bit-identical in every mode (env IRC_GEMM_PERSIST sets the
- * initial mode).  Returns the previous mode. */
+ * the results are bit-identical in every mode.  Returns the previous mode. */
 int irc_gemm_set_persistent(int mode);
 /* K loop of the 256 x 384 / 256 x 256 big-tile bf16 GEMM (QKV, out-proj, FFN2, the
  * LSTM input projections): 1 = a 4-slot ring of 32-deep K-tiles with three in flight,
  * 0 = two 64-deep slots (the default).  Same MFMAs in the same k order, so the
- * results are bit-identical (env IRC_BIG_RING sets the initial value).  Returns the
- * previous setting. */
+ * results are bit-identical.  Returns the previous setting. */
 int irc_gemm_set_big_ring(int on);
 /* LayerNorm-fold GEMM of the BERT encoder forward (bf16; HF BertLayer's
  * attention.output / intermediate / output sublayers, contrastive_module.py:39 ->
@@ -227,8 +228,8 @@ int irc_gemm_ln(int epilogue, int64_t M, int64_t N, int64_t K, const void* A, in
                 float* stats_out, int* stats_nt_out, irc_stream_t stream);
 /* MFMA shape of the big-tile kernel's 2-slot loop: 1 = v_mfma_f32_16x16x32_bf16 (the
  * default), 0 = v_mfma_f32_32x32x16_bf16.  Same products; the fp32 accumulation order
- * within a k32 step differs, so results agree within fp32 reassociation (env
- * IRC_BIG_MF16 sets the initial value).  Returns the previous setting. */
+ * within a k32 step differs, so results agree within fp32 reassociation.  Returns the
+ * previous setting. */
 int irc_gemm_set_big_mf16(int on);
 
 /* ------------------------------------------------------------- BERT encoder

@@ -22,6 +22,7 @@
 // along M/N and scattered into the [row][k] LDS image.  Blocks are remapped so
 // each XCD walks a contiguous band of output tiles (neighbours share A/B panels
 // in that XCD's L2).
+#include "gemm_epi.h"
 #include "gemm_pp.h"
 
 #include <algorithm>
@@ -36,16 +37,6 @@ namespace irc {
 namespace gemm {
 
 enum Layout { ROW = 0, COL = 1 };  // A: ROW=[M][K], COL=[K][M]; B: ROW=[N][K] (NK), COL=[K][N] (KN)
-// EPI_DGELU: C = alpha acc * gelu'(R)  (GELU backward; R = saved pre-activation)
-// EPI_BIAS_GELU_SAVE: C = gelu(alpha acc + bias) and R <- alpha acc + bias (R is a
-// second OUTPUT here: the pre-activation the GELU backward needs)
-enum Epi {
-  EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_BIAS_RESID = 3, EPI_RESID = 4,
-  EPI_DGELU = 5, EPI_BIAS_GELU_SAVE = 6
-};
-__host__ __device__ constexpr bool epi_has_bias(int e) {
-  return e == EPI_BIAS || e == EPI_BIAS_GELU || e == EPI_BIAS_RESID || e == EPI_BIAS_GELU_SAVE;
-}
 
 constexpr int BM = 128, BN = 128, NT = 256;
 
@@ -63,46 +54,6 @@ struct TT<float> {
   static constexpr int VEC = 4;
   static constexpr int PITCH = BK * 4 + 16;  // 64 + 16 pad
 };
-
-__device__ __forceinline__ float gelu_erf(float x) {
-  return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
-}
-
-// GELU(x) = 0.5 x (1 + erf(x / sqrt 2)) with erf from Abramowitz & Stegun 7.1.26
-// (|error| <= 1.5e-7 absolute, i.e. below fp32 resolution of the (1 + erf) sum
-// for |x| >~ 1): ~15 branch-free VALU ops against the library erff's ~40, which
-// matters when the epilogue is not hidden behind MFMA work (big-tile path).
-__device__ __forceinline__ float gelu_fast(float x) {
-  const float z = x * 0.70710678118654752f;
-  const float az = fabsf(z);
-  const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * az);
-  float p = 1.061405429f;
-  p = p * t - 1.453152027f;
-  p = p * t + 1.421413741f;
-  p = p * t - 0.284496736f;
-  p = p * t + 0.254829592f;
-  const float e = 1.0f - p * t * __expf(-az * az);
-  return 0.5f * x * (1.0f + copysignf(e, z));
-}
-
-// d/dx GELU(x) = Phi(x) + x phi(x), Phi via the same A&S 7.1.26 erf as gelu_fast.
-__device__ __forceinline__ float gelu_grad_fast(float x) {
-  const float z = x * 0.70710678118654752f;
-  const float az = fabsf(z);
-  const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * az);
-  float p = 1.061405429f;
-  p = p * t - 1.453152027f;
-  p = p * t + 1.421413741f;
-  p = p * t - 0.284496736f;
-  p = p * t + 0.254829592f;
-  const float ez = __expf(-az * az);
-  const float e = 1.0f - p * t * ez;
-  return 0.5f * (1.0f + copysignf(e, z)) + x * 0.3989422804014327f * ez;
-}
-__device__ __forceinline__ float gelu_grad_erf(float x) {
-  return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) +
-         x * 0.3989422804014327f * __expf(-0.5f * x * x);
-}
 
 struct Args {
   const void* A;
@@ -130,11 +81,6 @@ struct Args {
 // instead of scattering 2-byte LDS writes.
 __device__ __forceinline__ int kimg_off(int row, int ch) {
   return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
-typedef short v4s __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ v4s ds_tr16(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) v4s*)(p));
 }
 // 32x32x16 operand fragment (lane r32 = column, half h = k 8h..8h+7) of the 32
 // columns starting at col0, k-step ks, from a k-major image.
@@ -504,33 +450,6 @@ __device__ __forceinline__ void stage(const unsigned short* __restrict__ X, int6
     const int c = (p & 7) ^ chunk_key(row);     // logical k-chunk stored at this slot
     int gr = ls == 0 ? r0 + row
                      : ((r0 + row) >> sh) * ls + min(row & ((1 << sh) - 1), ls - 1);
-    gr = gr < nrows ? gr : nrows - 1;
-    glds16(X + (int64_t)gr * ld + k0 + c * 8, lds_tile + (i * NW + wave) * 1024);
-  }
-}
-// pass i of stage<ROWS> (i uniform; constant after unrolling)
-template <int ROWS>
-__device__ __forceinline__ void stage_one(int i, const unsigned short* __restrict__ X, int64_t ld,
-                                          int r0, int nrows, int k0, char* lds_tile, int wave,
-                                          int lane) {
-  const int p = (i * NW + wave) * 64 + lane;
-  const int row = p >> 3;
-  const int c = (p & 7) ^ chunk_key(row);
-  int gr = r0 + row;
-  gr = gr < nrows ? gr : nrows - 1;
-  glds16(X + (int64_t)gr * ld + k0 + c * 8, lds_tile + (i * NW + wave) * 1024);
-}
-// passes [P0, P1) of stage<ROWS> (spreading one K-tile's DMA over the k-steps)
-template <int ROWS, int P0, int P1>
-__device__ __forceinline__ void stage_part(const unsigned short* __restrict__ X, int64_t ld,
-                                           int r0, int nrows, int k0, char* lds_tile, int wave,
-                                           int lane) {
-#pragma unroll
-  for (int i = P0; i < P1; ++i) {
-    const int p = (i * NW + wave) * 64 + lane;
-    const int row = p >> 3;
-    const int c = (p & 7) ^ chunk_key(row);
-    int gr = r0 + row;
     gr = gr < nrows ? gr : nrows - 1;
     glds16(X + (int64_t)gr * ld + k0 + c * 8, lds_tile + (i * NW + wave) * 1024);
   }

@@ -30,6 +30,7 @@
 //  * Epilogue through LDS (per wave, 32-row passes) -> 16-byte coalesced stores,
 //    fused bias / GELU / GELU' / residual / pre-activation save / fp32 accumulate,
 //    or raw fp32 split-K slabs reduced afterwards in a fixed order.
+#include "gemm_epi.h"
 #include "gemm_pp.h"
 #include "mx.h"
 
@@ -38,14 +39,6 @@
 #include <mutex>
 
 namespace irc {
-namespace gemm {
-// shared with gemm.hip
-enum Epi {
-  EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_BIAS_RESID = 3, EPI_RESID = 4,
-  EPI_DGELU = 5, EPI_BIAS_GELU_SAVE = 6
-};
-}  // namespace gemm
-
 namespace gpp {
 using namespace irc::gemm;
 
@@ -78,72 +71,6 @@ constexpr int buf_bytes(bool ak, bool bk) { return 2 * slot_bytes(ak) + 2 * slot
 constexpr int LDS_BYTES = 2 * buf_bytes(false, false);  // 136 KB (allocation for all variants)
 constexpr int EP_PITCH = 68;          // epilogue staging row pitch (floats)
 
-__device__ __forceinline__ float gelu_f(float x) {
-  const float z = x * 0.70710678118654752f;
-  const float az = fabsf(z);
-  const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * az);
-  float p = 1.061405429f;
-  p = p * t - 1.453152027f;
-  p = p * t + 1.421413741f;
-  p = p * t - 0.284496736f;
-  p = p * t + 0.254829592f;
-  const float e = 1.0f - p * t * __expf(-az * az);
-  return 0.5f * x * (1.0f + copysignf(e, z));
-}
-// Two lanes' worth of gelu_f / gelu_grad_f on <2 x float>: the polynomial, scale and
-// blend steps issue as v_pk_fma_f32 / v_pk_mul_f32 (2 results per lane per op), only
-// rcp / exp / copysign stay scalar. Same operations in the same order as the scalar
-// forms, so the results are the same bits. The epilogue of the 256x256 tile is
-// VALU-bound (one workgroup per CU, nothing to overlap it with), so this is the
-// FFN1 + GELU launch's tail.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void erf_as_parts(f32x2 x, f32x2& z, f32x2& t, f32x2& ez) {
-  z = x * 0.70710678118654752f;
-  f32x2 az = {fabsf(z.x), fabsf(z.y)};
-  const f32x2 d = 1.0f + 0.3275911f * az;
-  t = f32x2{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-  const f32x2 n = -az * az;
-  ez = f32x2{__expf(n.x), __expf(n.y)};
-}
-__device__ __forceinline__ f32x2 erf_as_poly(f32x2 t) {
-  f32x2 p = 1.061405429f * t - 1.453152027f;
-  p = p * t + 1.421413741f;
-  p = p * t - 0.284496736f;
-  p = p * t + 0.254829592f;
-  return p;
-}
-__device__ __forceinline__ f32x2 gelu_f2(f32x2 x) {
-  f32x2 z, t, ez;
-  erf_as_parts(x, z, t, ez);
-  const f32x2 e = 1.0f - erf_as_poly(t) * t * ez;
-  const f32x2 s = {copysignf(e.x, z.x), copysignf(e.y, z.y)};
-  return 0.5f * x * (1.0f + s);
-}
-__device__ __forceinline__ f32x2 gelu_grad_f2(f32x2 x) {
-  f32x2 z, t, ez;
-  erf_as_parts(x, z, t, ez);
-  const f32x2 e = 1.0f - erf_as_poly(t) * t * ez;
-  const f32x2 s = {copysignf(e.x, z.x), copysignf(e.y, z.y)};
-  return 0.5f * (1.0f + s) + x * 0.3989422804014327f * ez;
-}
-__device__ __forceinline__ float gelu_grad_f(float x) {
-  const float z = x * 0.70710678118654752f;
-  const float az = fabsf(z);
-  const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * az);
-  float p = 1.061405429f;
-  p = p * t - 1.453152027f;
-  p = p * t + 1.421413741f;
-  p = p * t - 0.284496736f;
-  p = p * t + 0.254829592f;
-  const float ez = __expf(-az * az);
-  const float e = 1.0f - p * t * ez;
-  return 0.5f * (1.0f + copysignf(e, z)) + x * 0.3989422804014327f * ez;
-}
-
-__device__ __forceinline__ bool has_bias(int e) {
-  return e == EPI_BIAS || e == EPI_BIAS_GELU || e == EPI_BIAS_RESID || e == EPI_BIAS_GELU_SAVE;
-}
-
 // DMA one half-tile (128 rows/cols x 64 k) of operand X into `img`, by the 256
 // threads (4 waves, wave index wq) of one group: 4 wave-instructions each.
 //  KMAJOR: X[r][k] (row stride ld) rows r0..r0+127 (clamped to < nrows), k0..k0+63.
@@ -175,11 +102,6 @@ __device__ __forceinline__ void stage_half(const unsigned short* __restrict__ X,
       glds16(X + (int64_t)(k0 + 4 * blk + a) * ld + gc, img + blk * BPITCH);
     }
   }
-}
-
-typedef short v4s __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ v4s ds_tr16(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(p));
 }
 
 // 16x16x32 operand fragment: lane l gets X[row0 + (l & 15)][32 s + 8 (l >> 4) + j], j < 8.
@@ -454,7 +376,7 @@ __device__ __forceinline__ void epilogue_vec(const PArgs& g, const f32x4 (&acc)[
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int col = cbase + 16 * j + (lane & 15);
-      bv[j] = (!slab && has_bias(EPI) && col < g.N) ? bias[col] : 0.f;
+      bv[j] = (!slab && epi_has_bias(EPI) && col < g.N) ? bias[col] : 0.f;
     }
     const float alpha = slab ? 1.f : g.alpha;
     // LayerNorm fold (bf16 C only; uniform): the staged values are raw acc, the fold,
@@ -491,7 +413,7 @@ __device__ __forceinline__ void epilogue_vec(const PArgs& g, const f32x4 (&acc)[
       for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          f32x2 v[2];
+          f32x2_t v[2];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             if constexpr (F8 == 1)
@@ -561,7 +483,7 @@ __device__ __forceinline__ void epilogue_vec(const PArgs& g, const f32x4 (&acc)[
               if (EPI == EPI_BIAS_GELU) {
 #pragma unroll
                 for (int t = 0; t < 8; t += 2) {
-                  const f32x2 gg = gelu_lite2(f32x2{v[t], v[t + 1]});
+                  const f32x2_t gg = gelu_lite2(f32x2_t{v[t], v[t + 1]});
                   v[t] = gg.x;
                   v[t + 1] = gg.y;
                 }
@@ -585,7 +507,7 @@ __device__ __forceinline__ void epilogue_vec(const PArgs& g, const f32x4 (&acc)[
             } else if constexpr (EPI == EPI_DGELU) {
 #pragma unroll
               for (int t = 0; t < 8; t += 2) {
-                const f32x2 g2 = gelu_grad_f2(f32x2{bf16_to_f32(rr[t]), bf16_to_f32(rr[t + 1])});
+                const f32x2_t g2 = gelu_grad_f2(f32x2_t{bf16_to_f32(rr[t]), bf16_to_f32(rr[t + 1])});
                 v[t] *= g2.x;
                 v[t + 1] *= g2.y;
               }
@@ -600,7 +522,7 @@ __device__ __forceinline__ void epilogue_vec(const PArgs& g, const f32x4 (&acc)[
             for (int t = 0; t < 8; t += 2) {
               pre[t] = f32_to_bf16(v[t]);
               pre[t + 1] = f32_to_bf16(v[t + 1]);
-              const f32x2 g2 = gelu_f2(f32x2{v[t], v[t + 1]});
+              const f32x2_t g2 = gelu_f2(f32x2_t{v[t], v[t + 1]});
               v[t] = g2.x;
               v[t + 1] = g2.y;
             }
@@ -653,12 +575,12 @@ __device__ __forceinline__ void epilogue_vec(const PArgs& g, const f32x4 (&acc)[
           if (EPI == EPI_BIAS_RESID || EPI == EPI_RESID || EPI == EPI_DGELU) {
             const f32x4 r = *reinterpret_cast<const f32x4*>(R + (int64_t)row * g.ldr + col);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) v[t] = EPI == EPI_DGELU ? v[t] * gelu_grad_f(r[t]) : v[t] + r[t];
+            for (int t = 0; t < 4; ++t) v[t] = EPI == EPI_DGELU ? v[t] * gelu_grad_fast(r[t]) : v[t] + r[t];
           }
           if (EPI == EPI_BIAS_GELU_SAVE) {
             *reinterpret_cast<f32x4*>(const_cast<float*>(R) + (int64_t)row * g.ldr + col) = v;
 #pragma unroll
-            for (int t = 0; t < 4; ++t) v[t] = gelu_f(v[t]);
+            for (int t = 0; t < 4; ++t) v[t] = gelu_fast(v[t]);
           }
           float* dst = C + (int64_t)row * g.ldc + col;
           if (g.accumulate) v += *reinterpret_cast<const f32x4*>(dst);
@@ -959,7 +881,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
   for (int j = 0; j < 4; ++j) {
     const int col = cbase + 16 * j + (lane & 15);
     if (col >= g.N) continue;
-    const float bvv = has_bias(EPI) ? bias[col] : 0.f;
+    const float bvv = epi_has_bias(EPI) ? bias[col] : 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -967,14 +889,14 @@ __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
         const int row = rbase0 + 16 * i + 4 * (lane >> 4) + e;
         if (row >= g.M) continue;
         float v = acc[i][j][e] * g.alpha + bvv;
-        if (EPI == EPI_BIAS_GELU) v = sizeof(TO) == 2 ? gelu_lite(v) : gelu_f(v);
+        if (EPI == EPI_BIAS_GELU) v = sizeof(TO) == 2 ? gelu_lite(v) : gelu_fast(v);
         if (EPI == EPI_BIAS_GELU_SAVE) {
           TO* pre = const_cast<TO*>(R) + (int64_t)row * g.ldr + col;
           if constexpr (sizeof(TO) == 2)
             *reinterpret_cast<unsigned short*>(pre) = f32_to_bf16(v);
           else
             *reinterpret_cast<float*>(pre) = v;
-          v = gelu_f(v);
+          v = gelu_fast(v);
         }
         if (EPI == EPI_BIAS_RESID || EPI == EPI_RESID || EPI == EPI_DGELU) {
           float r;
@@ -982,7 +904,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
             r = bf16_to_f32(reinterpret_cast<const unsigned short*>(R)[(int64_t)row * g.ldr + col]);
           else
             r = reinterpret_cast<const float*>(R)[(int64_t)row * g.ldr + col];
-          v = EPI == EPI_DGELU ? v * gelu_grad_f(r) : v + r;
+          v = EPI == EPI_DGELU ? v * gelu_grad_fast(r) : v + r;
         }
         TO* dst = C + (int64_t)row * g.ldc + col;
         if constexpr (sizeof(TO) == 2) {
@@ -1262,11 +1184,6 @@ static void launch_layout(int la, int lb, int epi, const PArgs& a, dim3 grid, hi
 
 namespace irc {
 namespace gpp {
-
-int device_cu_count() {
-  const int n = cu_count();
-  return n > 0 ? n : 256;
-}
 
 // Split count: fill (at most) one wave of 256 blocks when the output tile grid
 // alone cannot (fp32 C, no fused epilogue), each K slice >= 1024 deep.

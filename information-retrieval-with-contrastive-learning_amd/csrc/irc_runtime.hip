@@ -28,7 +28,7 @@ int check_launch(const char* what) {
 
 extern "C" const char* irc_last_error(void) { return irc::g_err; }
 
-extern "C" int irc_abi_version(void) { return 1; }
+extern "C" int irc_abi_version(void) { return 2; }
 
 // ---------------------------------------------------------------- profiling
 // Optional per-kernel timing with HIP events recorded on the launch stream, used

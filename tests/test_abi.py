@@ -29,7 +29,7 @@ def test_binding_table_matches_header():
 
 def test_host_side_validation_without_gpu():
     lib = _lib.load()
-    assert lib.irc_abi_version() == 1
+    assert lib.irc_abi_version() == 2
     # bad D is rejected on the host before any launch
     rc = lib.irc_scan_topk(None, None, 4, 10, 100, 5, 0, None, 0, None, None, None)
     assert rc == 1001

@@ -1,4 +1,6 @@
 """irc_gemm (bf16 and exact-fp32 MFMA) vs a plain PyTorch fp32 reference of the same op."""
+import functools
+
 import pytest
 import torch
 
@@ -315,6 +317,80 @@ def test_big_tile_mf16_random_close(gpu):
     finally:
         ops.gemm_set_big_mf16(prev)
     assert (outs[0] - outs[1]).abs().max().item() <= 1e-4 * K ** 0.5
+
+
+@functools.lru_cache(maxsize=1)  # the epilogues of one shape run back to back
+def _exact_case(M, N, K):
+    """Small-integer operands of test_big_tile_exact and their product, computed on the
+    CPU: |sum| <= 16 K <= 49152, so every partial sum is an integer below 2^24 and the
+    fp32 product is exact in any summation order -- checked against the fp64 product."""
+    g = torch.Generator().manual_seed(M + N + K)
+    a = torch.randint(-4, 5, (M, K), generator=g).to(torch.bfloat16)
+    b = torch.randint(-4, 5, (N, K), generator=g).to(torch.bfloat16)
+    bias = torch.randint(-8, 9, (N,), generator=g).float() / 4
+    res = torch.randint(-8, 9, (M, N), generator=g).to(torch.bfloat16)
+    prod = a.float() @ b.float().t()
+    assert torch.equal(prod.double(), a.double() @ b.double().t())
+    return a, b, bias, res, prod
+
+
+@pytest.mark.parametrize("epi", [0, 1, 2, 3, 4])
+@pytest.mark.parametrize("M,N,K", [(32768, 2304, 768), (32768, 768, 3072), (32700, 2304, 192),
+                                   (4000, 2100, 640), (32668, 768, 192), (32700, 2304, 64)])
+def test_big_tile_exact(gpu, epi, M, N, K):
+    """The big-tile kernel as irc_gemm launches it by default, against the exact result
+    (an independent reference; the variant tests above only compare its K loops with each
+    other): the BERT QKV / FFN2 shapes, ragged M, a 256 x 256 case (N % 384 != 0), and
+    K = 192 / K = 64 (three K-tiles / a single one: nothing to prefetch).  Small-integer
+    operands, a bias of multiples of 1/4 and an integer residual keep every sum exact in
+    fp32 (on a 1/4 grid, below 2^16), so the bf16 output of epilogues 0, 1, 3, 4 equals the
+    rounded torch result bit for bit, and so does the fp32 output of epilogue 0 (the LSTM
+    input projection's form).  Epilogue 2 applies gelu_lite to the exact pre-activation:
+    the criterion of test_gelu_bf16_epilogue_matches_exact_erf_gelu against the exact erf
+    GELU (at most 1 bf16 ulp where |GELU| >= 1e-4, absolute error <= 1e-5 below)."""
+    from irc_amd import ops
+
+    a, b, bias, res, prod = (t.to(gpu) for t in _exact_case(M, N, K))
+    bias = bias if epi in (1, 2, 3) else None
+    res = res if epi in (3, 4) else None
+    out = ops.gemm(a, b, bias=bias, epilogue=epi, residual=res, out_dtype=torch.bfloat16)
+    pre = prod if bias is None else prod + bias
+    if epi == 2:
+        ref = torch.nn.functional.gelu(pre.double()).to(torch.bfloat16)
+        oi, ri = out.view(torch.int16).int(), ref.view(torch.int16).int()
+        same_sign = (out.float() * ref.float() >= 0)
+        ulps = torch.where(same_sign, (oi - ri).abs(), torch.full_like(oi, 1 << 20))
+        small = ref.float().abs() < 1e-4  # |GELU| < 1e-4: absolute error bound instead
+        worst_abs = (out.float() - ref.float()).abs()[small].max().item() if small.any() else 0.0
+        worst_ulp = ulps[~small].max().item()
+        print(f"gelu: max abs err below 1e-4 {worst_abs:.3g}, max ulps above {worst_ulp}")
+        assert worst_abs <= 1e-5
+        assert worst_ulp <= 1
+    else:
+        ref = pre if res is None else pre + res.float()
+        assert torch.equal(out, ref.to(torch.bfloat16))
+    if epi == 0:
+        assert torch.equal(ops.gemm(a, b, out_dtype=torch.float32), prod)
+
+
+def test_big_tile_random_close(gpu):
+    """Random bf16 operands (FFN2 shape, K = 3072, bias + residual, fp32 C) against the
+    fp64 result.  The bound is the project's own for this kernel, 1e-4 sqrt(K) absolute;
+    the fp32 accumulation error of a K = 3072 sum of magnitude ~1.7 is of the order of
+    1e-5, so it holds with two orders of margin."""
+    from irc_amd import ops
+
+    M, N, K = 32768, 768, 3072
+    g = torch.Generator().manual_seed(5)
+    a = torch.randn((M, K), generator=g).to(torch.bfloat16).to(gpu)
+    b = (torch.randn((N, K), generator=g) * 0.03).to(torch.bfloat16).to(gpu)
+    bias = torch.randn((N,), generator=g).to(gpu)
+    res = torch.randn((M, N), generator=g).to(gpu)
+    out = ops.gemm(a, b, bias=bias, epilogue=3, residual=res, out_dtype=torch.float32)
+    ref = a.double() @ b.double().t() + bias + res
+    err = (out - ref).abs().max().item()
+    print(f"max abs err vs fp64: {err:.3g}")
+    assert err <= 1e-4 * K ** 0.5
 
 
 @pytest.mark.parametrize("M,N", [(4096, 3072), (32768, 768), (300, 260)])

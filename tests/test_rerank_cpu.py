@@ -17,7 +17,7 @@ def _call(lib, D, k, Q=4, N=10, n_cand=0, ws=0):
 
 def test_rerank_rejects_bad_shapes_on_the_host():
     lib = _lib.load()
-    assert lib.irc_abi_version() == 1
+    assert lib.irc_abi_version() == 2
     assert _call(lib, 100, 5) == 1001
     assert b"unsupported D" in lib.irc_last_error()
     assert _call(lib, 128, 0) == 1001
