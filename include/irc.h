@@ -112,6 +112,25 @@ int irc_rerank_topk(const void* queries, const void* docs, int64_t Q, int64_t N,
                     float* out_score, int64_t* out_idx, int32_t* out_n, irc_stream_t stream);
 int irc_rerank_chunk(void);
 
+/* The same top-k by another scoring method, for dense lists: instead of gathering each
+ * candidate row once per (query, candidate), the shard streams once per 256-query tile
+ * through the MFMA GEMM loop and each query's candidates' scores are picked out of the
+ * 256 x 256 score tiles; a doc tile in which no query of the tile has a candidate is
+ * skipped.  Arguments, limits, workspace (irc_rerank_topk_workspace), validation and
+ * outputs are irc_rerank_topk's, with ONE MORE CONTRACT ON THE LISTS: every query's list
+ * is ASCENDING in global id (and unique), as irc_csr_union_emit writes it; ids of other
+ * shards are then a prefix and a suffix of the list.  A list that breaks the contract may
+ * be ranked wrongly; nothing is read or written out of bounds.  The ranking rule is the
+ * same and exact; a score may differ from irc_rerank_topk's in its last bits, because
+ * the fp32 summation order is the GEMM loop's (one fixed order per (query, doc) too).
+ * irc_rerank_stream_tile: the doc-tile width (test / tuning aid). */
+int irc_rerank_topk_stream(const void* queries, const void* docs, int64_t Q, int64_t N,
+                           int64_t D, const int32_t* cand, const int64_t* cand_off,
+                           int64_t n_cand, int64_t k, int64_t doc_offset, void* workspace,
+                           int64_t workspace_bytes, float* out_score, int64_t* out_idx,
+                           int32_t* out_n, irc_stream_t stream);
+int irc_rerank_stream_tile(void);
+
 /* Raw score tile for tests / diagnostics: out[Q, N] fp32 = queries . docs^T
  * using the same MFMA path as irc_scan_topk. */
 int irc_scan_scores(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,

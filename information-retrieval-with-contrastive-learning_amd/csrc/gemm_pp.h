@@ -82,6 +82,14 @@ struct PArgs {
   unsigned char* cx;
   // LayerNorm fold (bf16 C, vectorised epilogue, non-persistent): ln.st == null = off
   LnArgs ln;
+  // candidate pick (EPI_PICK, run_pick): query q owns the global doc ids
+  // cand[cand_off[q] .. cand_off[q + 1]), ascending and unique; candidate j whose id lies
+  // in this shard, [doc_offset, doc_offset + N), gets keys[j] = make_key(C[q][id -
+  // doc_offset], id) (`keys` above, n_cand entries).  Other entries are not written.
+  const int32_t* cand;
+  const int64_t* cand_off;
+  int64_t n_cand;
+  int64_t doc_offset;
 };
 
 int splits_for(int out_f32, int epi, int64_t M, int64_t N, int64_t K, int64_t batch,
@@ -97,6 +105,11 @@ void run(int out_f32, int la, int lb, int epi, const PArgs& a, int64_t batch, in
 // scan filter: A = queries [M=Q][K=D], B = docs [N][D] (row stride ldb), EPI_SCAN;
 // fp8: e4m3 operands, K / lda / ldb in 2-byte units (D/2)
 void run_scan(const PArgs& a, hipStream_t st, bool fp8 = false);
+// candidate pick: A = queries [M=Q][K=D], B = docs [N][D], bf16, EPI_PICK (see PArgs);
+// M, N > 0 and ceil(M / 256) * ceil(N / 256) < 2^31
+void run_pick(const PArgs& a, hipStream_t st);
+// doc-tile width of run_pick
+constexpr int PICK_TILE = 256;
 // raw fp32 C = A . B^T of e4m3 operands (K, lda, ldb in 2-byte units; vec_c layout)
 void run_scores_fp8(const PArgs& a, hipStream_t st);
 // e4m3 linear layer: bf16 C = (A8 . B8^T) * sa[m] * sb[n] (+ bias / GELU / residual);

@@ -798,6 +798,113 @@ __device__ __forceinline__ void epilogue_scan_lists(const PArgs& g, const f32x4 
   }
 }
 
+// Candidate pick (EPI_PICK, irc_rerank_topk_stream): one 256-query x 256-doc tile of
+// queries . docs^T, of which only the scores of each query's own candidates are kept --
+// as 64-bit keys at the candidates' own places in the CSR-ordered keys[] that
+// rerank_select_kernel (rerank.hip) ranks.  The lists are ascending in global id, so the
+// candidates of query q that fall into this doc tile are one contiguous range [lo, hi) of
+// its list: two lower bounds per query, taken BEFORE the main loop and kept in the 8 KB
+// of LDS past the two K-major K-tile buffers (which the bf16 main loop never touches).  A
+// tile no query of which has a candidate in it returns there, without the main loop.
+constexpr int PICK_OFF = 2 * buf_bytes(true, true);  // 128 KB
+static_assert(PICK_OFF + 2 * BM * 8 + 16 <= LDS_BYTES, "pick ranges past the K-tile buffers");
+
+// lo / hi of the tile's 256 queries -> LDS; false: every range is empty (workgroup-uniform)
+__device__ __forceinline__ bool pick_ranges(const PArgs& g, char* lds, int m0, int n0) {
+  int64_t* plo = reinterpret_cast<int64_t*>(lds + PICK_OFF);
+  int64_t* phi = plo + BM;
+  int* any = reinterpret_cast<int*>(phi + BM);
+  const int tid = threadIdx.x;
+  if (tid == 0) *any = 0;
+  lds_barrier();
+  if (tid < BM) {
+    const int q = m0 + tid;
+    int64_t lo = 0, hi = 0;
+    if (q < g.M) {
+      // clamped as rerank_select_kernel clamps them: keys[] and cand[] hold n_cand entries
+      int64_t c0 = g.cand_off[q], c1 = g.cand_off[q + 1];
+      c1 = c1 < g.n_cand ? c1 : g.n_cand;
+      c0 = c0 < 0 ? 0 : c0;
+      c0 = c0 < c1 ? c0 : c1;
+      const int64_t first = g.doc_offset + n0;
+      const int64_t last = g.doc_offset + (n0 + BN < g.N ? n0 + BN : g.N);  // exclusive
+      // two independent lower bounds (one latency per step); both stay in [c0, c1]
+      // whatever the list holds
+      int64_t la = c0, ha = c1, lb = c0, hb = c1;
+      while (la < ha || lb < hb) {
+        if (la < ha) {
+          const int64_t mid = la + ((ha - la) >> 1);
+          if ((int64_t)g.cand[mid] < first) la = mid + 1;
+          else ha = mid;
+        }
+        if (lb < hb) {
+          const int64_t mid = lb + ((hb - lb) >> 1);
+          if ((int64_t)g.cand[mid] < last) lb = mid + 1;
+          else hb = mid;
+        }
+      }
+      lo = la;
+      hi = lb;
+    }
+    plo[tid] = lo;
+    phi[tid] = hi;
+    if (lo < hi) *any = 1;
+  }
+  lds_barrier();
+  return *any != 0;
+}
+
+// Four passes of 64 queries, staged as epilogue_scan_lists stages them (64 x 256 fp32,
+// column c of row r at c ^ 32 (r & 1)); then the 8 lanes of thread group t >> 3 walk
+// query t >> 3's range [lo, hi), 4 candidate ids in flight per lane: candidate j's score
+// is read from the staged row at its column and its key goes to keys[j].  Nothing
+// depends on scheduling (no atomics: j is the candidate's own place).  A column outside
+// the tile (a list that broke the ascending contract) is skipped before any access.
+__device__ __forceinline__ void epilogue_pick(const PArgs& g, const f32x4 (&acc)[8][4], char* lds,
+                                              int m0, int n0, int grp, int wn, int lane) {
+  float* S = reinterpret_cast<float*>(lds);
+  const int64_t* plo = reinterpret_cast<const int64_t*>(lds + PICK_OFF);
+  const int64_t* phi = plo + BM;
+  const int tid = threadIdx.x;
+  const int rq = tid >> 3, seg = tid & 7, flip = (rq & 1) << 5;
+  const int64_t nval = g.N - n0 < BN ? g.N - n0 : BN;  // docs of this tile
+  const int64_t first = g.doc_offset + n0;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    if (grp == (p >> 1)) {
+#pragma unroll
+      for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int r = 16 * ii + 4 * (lane >> 4) + e;
+            const int c = (64 * wn + 16 * j + (lane & 15)) ^ ((e & 1) << 5);
+            S[r * 256 + c] = acc[4 * (p & 1) + ii][j][e];
+          }
+    }
+    lds_barrier();
+    const int64_t lo = plo[64 * p + rq], hi = phi[64 * p + rq];  // padded rows: lo == hi
+    const float* row = S + rq * 256;
+    for (int64_t j0 = lo + seg; j0 < hi; j0 += 32) {
+      int32_t id[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t j = j0 + 8 * u;
+        id[u] = j < hi ? g.cand[j] : 0;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t j = j0 + 8 * u;
+        const int64_t col = (int64_t)id[u] - first;
+        if (j < hi && col >= 0 && col < nval)
+          g.keys[j] = make_key(row[(int)col ^ flip], (uint32_t)id[u]);
+      }
+    }
+    lds_barrier();  // every reader is done with S before the next pass writes it
+  }
+}
+
 template <bool AK, bool BK_, typename TO, int EPI, int F8 = 0, bool LN = false>
 __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
   __shared__ __attribute__((aligned(1024))) char lds[LDS_BYTES];
@@ -822,10 +929,10 @@ __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
     split = rest % gridDim.z;
     batch = rest / gridDim.z;
   }
-  // EPI_SCAN: query tiles fastest, so the blocks of one doc tile run back to back
-  // on one XCD and read it from that XCD's L2 (C4: 2048 queries = 8 query tiles)
+  // EPI_SCAN (and EPI_PICK): query tiles fastest, so the blocks of one doc tile run back
+  // to back on one XCD and read it from that XCD's L2 (C4: 2048 queries = 8 query tiles)
   int tm, tn;
-  if (EPI == EPI_SCAN) {
+  if (EPI == EPI_SCAN || EPI == EPI_PICK) {
     tm = bid % tiles_m;
     tn = bid / tiles_m;
   } else {
@@ -843,6 +950,10 @@ __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
   const int wn = wq;                          // 64-column slab of the tile
 
   if (EPI == EPI_SCAN) PSTAMP(0);
+  if constexpr (EPI == EPI_PICK) {
+    static_assert(AK && BK_ && F8 == 0, "the pick ranges live past two K-major buffers");
+    if (!pick_ranges(g, lds, m0, n0)) return;  // no candidate in this tile
+  }
   f32x4 acc[8][4];
   mainloop<AK, BK_, F8>(g, A, B, m0, n0, kbeg, nk, lds, buf_bytes(AK, BK_), 0, false, acc, grp,
                         wq, lane, nullptr, 0);
@@ -856,6 +967,10 @@ __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
       epilogue_scan_lists(g, acc, lds, m0, n0, tn, grp, wn, lane, [] {});
     else
       epilogue_scan(g, acc, lds, m0, n0, tn, grp, wn, lane, [] {});
+    return;
+  }
+  if constexpr (EPI == EPI_PICK) {
+    epilogue_pick(g, acc, lds, m0, n0, grp, wn, lane);
     return;
   }
 #ifdef IRC_PP_DIAG_NOEPI  // diagnostic build: main loop only (a guarded store of the sum of
@@ -1120,6 +1235,12 @@ void run_scan(const PArgs& a, hipStream_t st, bool fp8) {
   else
     hipLaunchKernelGGL((gemm_pp_kernel<true, true, float, EPI_SCAN>), dim3((unsigned)tiles),
                        dim3(NT), 0, st, a);
+}
+
+void run_pick(const PArgs& a, hipStream_t st) {
+  const int64_t tiles = ((int64_t)(a.M + 255) / 256) * ((a.N + 255) / 256);
+  hipLaunchKernelGGL((gemm_pp_kernel<true, true, float, EPI_PICK>), dim3((unsigned)tiles),
+                     dim3(NT), 0, st, a);
 }
 
 void run_scores_fp8(const PArgs& a, hipStream_t st) {

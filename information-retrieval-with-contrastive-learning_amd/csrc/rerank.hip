@@ -27,8 +27,14 @@
 //    re-read per digit until the selected bucket fits, and the pass that moves the bucket
 //    to LDS also collects the keys above it, so nothing is read after that.  Keys are
 //    distinct (unique ids), so exactly min(k, eligible) keys reach the k-th.
+//  * irc_rerank_topk_stream fills the same keys[] another way, for dense lists: the shard
+//    streams once per 256-query tile through the ping-pong MFMA GEMM loop and each
+//    query's candidates are picked out of the score tile (gemm_pp.hip, EPI_PICK; lists
+//    ascending in global id).  rerank_foreign_kernel zeroes the keys of the ids outside
+//    the shard, a prefix and a suffix of every list; the select is the same kernel.
 #include <stdint.h>
 
+#include "gemm_pp.h"
 #include "irc_common.h"
 
 namespace irc {
@@ -396,6 +402,41 @@ __global__ __launch_bounds__(SNT) void rerank_select_kernel(
   if (tid == 0) out_n[q] = cnt;
 }
 
+// Stream method: keys of the candidates of other shards.  With ascending lists the ids
+// below doc_offset are a prefix of each list and those from doc_offset + N on a suffix;
+// the pick kernel writes every key between the two and none of these.  One query per
+// blockIdx.x, its prefix and suffix spread over the gridDim.y workgroups.  Both bounds
+// stay in [c0, c1] whatever the list holds.
+constexpr int RF_NT = 256;
+constexpr int RF_Y = 8;
+__global__ __launch_bounds__(RF_NT) void rerank_foreign_kernel(
+    const int32_t* __restrict__ cand, const int64_t* __restrict__ cand_off, int64_t n_cand,
+    int64_t doc_offset, int64_t N, uint64_t* __restrict__ keys) {
+  const int64_t q = blockIdx.x;
+  int64_t c0 = cand_off[q], c1 = cand_off[q + 1];
+  c1 = c1 < n_cand ? c1 : n_cand;
+  c0 = c0 < 0 ? 0 : c0;
+  c0 = c0 < c1 ? c0 : c1;
+  const int64_t first = doc_offset, last = doc_offset + N;
+  int64_t la = c0, ha = c1, lb = c0, hb = c1;
+  while (la < ha || lb < hb) {
+    if (la < ha) {
+      const int64_t mid = la + ((ha - la) >> 1);
+      if ((int64_t)cand[mid] < first) la = mid + 1;
+      else ha = mid;
+    }
+    if (lb < hb) {
+      const int64_t mid = lb + ((hb - lb) >> 1);
+      if ((int64_t)cand[mid] < last) lb = mid + 1;
+      else hb = mid;
+    }
+  }
+  const int64_t pre = la - c0, total = pre + (c1 - lb);
+  for (int64_t i = (int64_t)blockIdx.y * RF_NT + threadIdx.x; i < total;
+       i += (int64_t)RF_Y * RF_NT)
+    keys[i < pre ? c0 + i : lb + (i - pre)] = 0ull;
+}
+
 static bool supported_d(int64_t D) {  // the scan's set (scan_topk.hip)
   return D == 64 || D == 128 || D == 256 || D == 384 || D == 512 || D == 768 || D == 1024;
 }
@@ -417,6 +458,19 @@ extern "C" int64_t irc_rerank_topk_workspace(int64_t Q, int64_t n_cand, int64_t 
   (void)Q;
   (void)k;
   return (int64_t)workspace_bytes_for(n_cand);
+}
+
+extern "C" int irc_rerank_stream_tile(void) { return gpp::PICK_TILE; }
+
+// The two scoring methods share the select launch.
+static int launch_select(const uint64_t* keys, const int64_t* cand_off, int64_t Q, int64_t n_cand,
+                         int64_t k, float* out_score, int64_t* out_idx, int32_t* out_n,
+                         hipStream_t st) {
+  prof_begin(st);
+  hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)Q), dim3(SNT), 0, st, keys, cand_off,
+                     n_cand, (int)k, out_score, out_idx, out_n);
+  prof_end("rerank_select", st, (double)n_cand * 8.0);
+  return check_launch("rerank_select_kernel");
 }
 
 extern "C" int irc_rerank_topk(const void* queries, const void* docs, int64_t Q, int64_t N,
@@ -467,9 +521,63 @@ extern "C" int irc_rerank_topk(const void* queries, const void* docs, int64_t Q,
     prof_end("rerank_score", st, (double)n_cand * D * 2.0);  // the gathered row bytes
     if (int rc = check_launch("rerank_score_kernel")) return rc;
   }
-  prof_begin(st);
-  hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)Q), dim3(SNT), 0, st, keys, cand_off,
-                     n_cand, (int)k, out_score, out_idx, out_n);
-  prof_end("rerank_select", st, (double)n_cand * 8.0);
-  return check_launch("rerank_select_kernel");
+  return launch_select(keys, cand_off, Q, n_cand, k, out_score, out_idx, out_n, st);
+}
+
+extern "C" int irc_rerank_topk_stream(const void* queries, const void* docs, int64_t Q,
+                                      int64_t N, int64_t D, const int32_t* cand,
+                                      const int64_t* cand_off, int64_t n_cand, int64_t k,
+                                      int64_t doc_offset, void* workspace,
+                                      int64_t workspace_bytes, float* out_score,
+                                      int64_t* out_idx, int32_t* out_n, irc_stream_t stream) {
+  // irc_rerank_topk's checks, in its order
+  IRC_REQUIRE(Q >= 0 && N >= 0 && n_cand >= 0, "rerank_topk: negative size");
+  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "rerank_topk: k=%lld outside [1, %d]", (long long)k,
+              RR_MAXK);
+  IRC_REQUIRE(supported_d(D), "rerank_topk: unsupported D=%lld", (long long)D);
+  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
+              "rerank_topk: global doc ids must fit int32 (doc_offset + N < 2^31)");
+  IRC_REQUIRE(Q < (1ll << 31) - 1, "rerank_topk: Q too large");
+  IRC_REQUIRE(n_cand < (1ll << 31) * RR_CHUNK, "rerank_topk: n_cand too large");
+  // one workgroup per (query tile, doc tile): the grid and the kernel's int tile count
+  IRC_REQUIRE(((Q + 255) / 256) * ((N + 255) / 256) < (1ll << 31),
+              "rerank_topk: Q x N too large for the stream method");
+  if (workspace == nullptr || workspace_bytes < (int64_t)workspace_bytes_for(n_cand)) {
+    set_error("rerank_topk: workspace %lld < required %lld bytes", (long long)workspace_bytes,
+              (long long)workspace_bytes_for(n_cand));
+    return IRC_E_WORKSPACE;
+  }
+  if (Q == 0) return IRC_OK;
+  IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n, "rerank_topk: null pointer");
+  IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)), "rerank_topk: null candidates / docs");
+  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
+              "rerank_topk: queries and docs must be 16-byte aligned");
+  hipStream_t st = as_stream(stream);
+  uint64_t* keys = static_cast<uint64_t*>(workspace);
+  if (n_cand > 0) {
+    prof_begin(st);
+    hipLaunchKernelGGL(rerank_foreign_kernel, dim3((unsigned)Q, RF_Y), dim3(RF_NT), 0, st, cand,
+                       cand_off, n_cand, doc_offset, N, keys);
+    if (N > 0) {
+      gpp::PArgs a{};
+      a.A = static_cast<const unsigned short*>(queries);
+      a.B = static_cast<const unsigned short*>(docs);
+      a.M = (int)Q;
+      a.N = (int)N;
+      a.K = (int)D;
+      a.kchunk = a.K;
+      a.lda = D;
+      a.ldb = D;
+      a.keys = keys;
+      a.cand = cand;
+      a.cand_off = cand_off;
+      a.n_cand = n_cand;
+      a.doc_offset = doc_offset;
+      gpp::run_pick(a, st);
+    }
+    // the bytes the pass streams: the shard once per query tile
+    prof_end("rerank_stream_score", st, (double)((Q + 255) / 256) * (double)N * D * 2.0);
+    if (int rc = check_launch("rerank_stream_score")) return rc;
+  }
+  return launch_select(keys, cand_off, Q, n_cand, k, out_score, out_idx, out_n, st);
 }

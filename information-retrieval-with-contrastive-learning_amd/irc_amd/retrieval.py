@@ -177,11 +177,75 @@ def __getattr__(name):
     # list lengths around it are the kernel's edge cases.
     if name == "RERANK_CHUNK":
         return int(_lib.load().irc_rerank_chunk())
+    # RERANK_STREAM_TILE: the doc-tile width of irc_rerank_topk_stream
+    # (irc_rerank_stream_tile(), gpp::PICK_TILE in csrc/gemm_pp.h), read the same way.
+    if name == "RERANK_STREAM_TILE":
+        return int(_lib.load().irc_rerank_stream_tile())
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
+RERANK_METHODS = ("gather", "stream")
+
+# Candidates per query, as a fraction of the shard, from which method="stream" is the
+# faster call, per query count Q: the gather-against-stream ``crossover_frac`` of
+# profiles/rerank_stream_probe.json (tools/rerank_probe.py; one MI355X, 250k x 768 shard,
+# k = 100).  None: gather was faster in every measured cell of that Q (up to 25 %).
+_STREAM_CROSSOVER = ((1, None), (16, 0.15634670821855476), (64, 0.03685017313384864),
+                     (256, 0.010609454861342326))
+_STREAM_MIN_TILES = 4  # below this many doc tiles the shard is too small to matter
+
+
+def rerank_method(Q: int, N: int, D: int, n_cand: int) -> str:
+    """"gather" or "stream": the faster scoring method of ``rerank_topk`` for Q queries
+    with n_cand candidates in all against a shard of N docs (pure host arithmetic, no
+    device access).  "stream" once the mean list length n_cand / Q reaches the measured
+    crossover fraction of the shard for that Q -- the ``crossover_frac`` entries of
+    profiles/rerank_stream_probe.json, interpolated log-log between the measured Q = 1,
+    16, 64, 256 and held constant beyond them; where gather won every measured cell of a
+    Q (Q = 1), and between such a Q and the next measured one, the answer is "gather".  A shard below 4 doc tiles (RERANK_STREAM_TILE docs each) is
+    always gathered.  The crossovers were measured at D = 768; both methods' scoring cost
+    is proportional to D, so D does not enter.  Monotone in n_cand."""
+    import math
+
+    if Q <= 0 or n_cand <= 0 or N < _STREAM_MIN_TILES * 256:
+        return "gather"
+    pts = _STREAM_CROSSOVER
+    if Q <= pts[0][0]:
+        frac = pts[0][1]
+    elif Q >= pts[-1][0]:
+        frac = pts[-1][1]
+    else:
+        frac = None
+        for (qa, fa), (qb, fb) in zip(pts, pts[1:]):
+            if qa <= Q <= qb:
+                if Q == qa:
+                    frac = fa
+                elif Q == qb:
+                    frac = fb
+                elif fa is not None and fb is not None:
+                    t = (math.log(Q) - math.log(qa)) / (math.log(qb) - math.log(qa))
+                    frac = math.exp(math.log(fa) + t * (math.log(fb) - math.log(fa)))
+                break
+    if frac is None:
+        return "gather"
+    return "stream" if n_cand >= frac * N * Q else "gather"
+
+
+def _sort_lists(cand: torch.Tensor, cand_off: torch.Tensor) -> torch.Tensor:
+    """Every list of the CSR pair ascending, in one device sort of (owner, id) pairs; no
+    host synchronisation.  cand int32 / int64 with values in [-2^31, 2^31)."""
+    n = cand.numel()
+    Q = cand_off.numel() - 1
+    lengths = cand_off[1:] - cand_off[:-1]
+    owner = torch.repeat_interleave(torch.arange(Q, device=cand.device), lengths, output_size=n)
+    key = (owner << 32) + (cand.to(torch.int64) + 2 ** 31)
+    key, _ = torch.sort(key)
+    return ((key & 0xFFFFFFFF) - 2 ** 31).to(torch.int32)
+
+
 def rerank_topk(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
-                cand_off: torch.Tensor, k: int, doc_offset: int = 0, ws_tag: str = "rerank"):
+                cand_off: torch.Tensor, k: int, doc_offset: int = 0, ws_tag: str = "rerank",
+                method: str = "gather", ascending: bool = False):
     """Exact top-k of each query over ITS OWN candidate docs (sparse filter, dense rerank:
     src/evaluation.py:57-83 feeding :110-112).
 
@@ -191,7 +255,21 @@ def rerank_topk(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
     within a list, in any order; ids outside the shard are skipped (an int64 id that does
     not fit int32 is in no shard and is skipped too, never wrapped).  Returns (scores fp32
     [Q, k], idx int64 [Q, k], n int32 [Q]): each list by (score desc, id asc), slots past
-    n[q] = min(k, eligible) are (-inf, -1)."""
+    n[q] = min(k, eligible) are (-inf, -1).
+
+    ``method="gather"`` (irc_rerank_topk) reads each candidate row once per (query,
+    candidate); ``method="stream"`` (irc_rerank_topk_stream) streams the shard once per
+    256-query tile through the MFMA GEMM loop and picks the candidates' scores out of the
+    score tiles -- the faster one for dense lists (``rerank_method``).  Same exact ranking
+    rule; a score may differ in its last bits between the two (another fp32 summation
+    order, each fixed per (query, doc)).  The stream kernel needs every list ASCENDING in
+    global id: ``ascending=True`` states that they are (``SparseIndex.candidates`` and
+    ``expand_ranges`` leave them so); otherwise they are sorted on the device first (one
+    ``torch.sort``, no host synchronisation) and the result is the same.  Under "stream"
+    an int64 id outside int32 is clamped to -1 / 2^31 - 1, which no shard owns, so an
+    ascending list stays ascending."""
+    if method not in RERANK_METHODS:
+        raise ValueError(f"method must be one of {RERANK_METHODS}, not {method!r}")
     require_hip(queries, docs, cand, cand_off)
     q = contig(queries, torch.bfloat16)
     d = contig(docs, torch.bfloat16)
@@ -205,16 +283,22 @@ def rerank_topk(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
         raise ValueError(f"cand_off has {cand_off.numel()} entries for {Q} queries (Q + 1)")
     if cand.dtype == torch.int64:
         # an id outside int32 is in no shard (doc_offset + N < 2^31): it must not wrap into one
-        cand = torch.where((cand < 0) | (cand >= 2 ** 31), cand.new_full((), -1), cand)
-    c = contig(cand, torch.int32)
+        if method == "stream":  # order-preserving
+            cand = cand.clamp(-1, 2 ** 31 - 1)
+        else:
+            cand = torch.where((cand < 0) | (cand >= 2 ** 31), cand.new_full((), -1), cand)
     off = contig(cand_off, torch.int64)
+    if method == "stream" and not ascending:
+        cand = _sort_lists(cand.reshape(-1), off)
+    c = contig(cand, torch.int32)
     n_cand = c.numel()
     out_s = torch.empty((Q, k), dtype=torch.float32, device=q.device)
     out_i = torch.empty((Q, k), dtype=torch.int64, device=q.device)
     out_n = torch.empty((Q,), dtype=torch.int32, device=q.device)
     nbytes = int(_lib.fn("irc_rerank_topk_workspace")(Q, n_cand, k))
     ws = workspace(nbytes, q.device, ws_tag)
-    _lib.call("irc_rerank_topk", ptr(q), ptr(d), Q, N, D, ptr(c), ptr(off), n_cand, k,
+    entry = "irc_rerank_topk_stream" if method == "stream" else "irc_rerank_topk"
+    _lib.call(entry, ptr(q), ptr(d), Q, N, D, ptr(c), ptr(off), n_cand, k,
               doc_offset, ptr(ws), ws.numel(), ptr(out_s), ptr(out_i), ptr(out_n),
               stream_ptr(q.device))
     return out_s, out_i, out_n
@@ -347,20 +431,38 @@ class ShardedDenseIndex:
         return self._exchange_merge(s, i, k)  # (3)
 
     def search_candidates(self, queries: torch.Tensor, cand: torch.Tensor,
-                          cand_off: torch.Tensor, k: int, ws_tag: str = "rerank"):
+                          cand_off: torch.Tensor, k: int, ws_tag: str = "rerank",
+                          method: str = "gather", ascending: bool = False):
         """Top-k of each query over its own candidate docs only (global ids, the CSR pair
         ``SparseIndex.candidates`` / ``expand_ranges`` leave on the device): (scores
         [Q, k], idx [Q, k], n [Q]) as ``rerank_topk``.  bf16 shards, single process.
 
-        Cost model: the candidate rows are gathered whole, once per
-        (query, candidate), with no reuse across queries -- n_cand * D * 2 bytes -- while
-        ``search`` streams the shard once for the whole batch.  So this call wins while
-        the lists are sparse and loses once they are dense; it is the only one of the two
-        that ranks the candidates alone.
+        ``method``: "gather" (the default), "stream", or "auto", which takes
+        ``rerank_method``'s choice when ``ascending=True`` and "gather" otherwise;
+        ``ascending`` as in ``rerank_topk``.
 
-        Measured (tools/rerank_probe.py, profiles/rerank_probe.json: one MI355X, 250k x 768
-        shard, random lists redrawn call by call, k = 100; call times in us, this call /
-        ``search``; ``tools/rerank_probe.py --tables`` prints this from the file):
+        Cost model: "gather" reads the candidate rows whole, once per
+        (query, candidate), with no reuse across queries -- n_cand * D * 2 bytes -- while
+        ``search`` streams the shard once for the whole batch.  "stream" does the latter for
+        the candidates alone: the shard goes once per 256 queries through the same MFMA
+        GEMM loop and each query's candidates are picked out of the score tiles.  Measured
+        on the 250k x 768 shard (profiles/rerank_stream_probe.json, call times in us,
+        gather / stream; ``tools/rerank_probe.py --tables`` prints this from the file):
+
+            candidates per query     Q = 1         Q = 16        Q = 64        Q = 256
+                 250 (0.1 %)         20 / 66       26 / 126      27 / 130       32 / 152
+               2,500 (1 %)           26 / 130      31 / 139      54 / 143      158 / 166
+              12,500 (5 %)           36 / 146      74 / 154     199 / 159      690 / 189
+              62,500 (25 %)          74 / 189     270 / 200     876 / 213    3,300 / 300
+
+        The gathered call grows with n_cand, the streamed one stays within 1.2-1.4x of a
+        full scan plus the select: they cross at 1.1 % of the shard per query at Q = 256,
+        3.7 % at Q = 64, 15.6 % at Q = 16, and gather wins throughout at Q = 1.  Either way
+        this is the only call that ranks the candidates alone.
+
+        Against the scan (tools/rerank_probe.py, profiles/rerank_probe.json: one MI355X, 250k x
+        768 shard, random lists redrawn call by call, k = 100; call times in us, the gathered
+        call / ``search``; ``tools/rerank_probe.py --tables`` prints this from the file):
 
             candidates per query     Q = 1         Q = 16        Q = 64        Q = 256
                  250 (0.1 %)         20 / 80       25 / 84       27 / 95        32 / 165
@@ -368,7 +470,7 @@ class ShardedDenseIndex:
               12,500 (5 %)           36 / 80       74 / 84      200 / 94       691 / 164
               62,500 (25 %)          74 / 80      271 / 84      876 / 94     3,303 / 164
 
-        The two cross at about 1.0 % of the shard per query at Q = 256, 2.0 % at Q = 64,
+        These two cross at about 1.0 % of the shard per query at Q = 256, 2.0 % at Q = 64,
         5.8 % at Q = 16, and above 25 % at Q = 1.  The scoring pass gathers 4.8-7.6 TB/s of
         row bytes from 160k candidates up (lists of one call that overlap hit the caches)
         and is latency-bound below."""
@@ -379,7 +481,12 @@ class ShardedDenseIndex:
                 "search_candidates over a process group: the all_gather of the queries and "
                 "candidate lists and of the per-shard top-k lists (search()'s collectives) "
                 "is not built; the per-shard rerank_topk call already skips foreign ids")
-        return rerank_topk(queries, self.docs, cand, cand_off, k, self.doc_offset, ws_tag=ws_tag)
+        if method == "auto":
+            # the stream method's sort of unsorted lists is not in the measured crossovers
+            method = "gather" if not ascending else rerank_method(
+                queries.shape[0], self.docs.shape[0], self.docs.shape[1], cand.numel())
+        return rerank_topk(queries, self.docs, cand, cand_off, k, self.doc_offset, ws_tag=ws_tag,
+                           method=method, ascending=ascending)
 
     # The three steps of a sharded search, separately callable (bench.py times each).
     def _sharded(self):

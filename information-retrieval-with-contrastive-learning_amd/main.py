@@ -3,6 +3,7 @@
     python main.py [--config config.yaml] [--data doc|fever] [--gpu 0] [--ckpt X]
                    [--model LSTM|BERT] [--loss InfoNCE] [--opt adam] [--sample uniform|tf_idf]
                    [--seed 1337] [--logdir log] [--ckptdir ckpt] [--retrieval sparse|dense|hybrid]
+                   [--rerank-method auto|gather|stream]
 
 Multi-GPU (one process per GPU):
     torchrun --nproc-per-node N --master-addr 127.0.0.1 main.py [same flags]
@@ -58,6 +59,15 @@ def get_args(argv=None):
                    help="--data fever: sparse n-gram filter as the reference (default), "
                         "dense bi-encoder top-k (superset), or hybrid: the filter's "
                         "candidates reranked by the bi-encoder (the reference's two stages)")
+    p.add_argument("--rerank-method", default="auto", type=str,
+                   choices=["auto", "gather", "stream"],
+                   help="--retrieval hybrid: how the candidates are scored. gather reads "
+                        "each candidate row per claim, stream runs the corpus through the "
+                        "MFMA GEMM once per 256 claims and picks the candidates' scores "
+                        "(faster for dense lists), auto picks per batch from measured "
+                        "crossovers. Same ranking contract either way: the exact top-k over "
+                        "the candidates only; scores may differ in the last bits (another "
+                        "fp32 summation order)")
     return p.parse_args(argv)
 
 

@@ -170,18 +170,20 @@ def hybrid_corpus(wiki, doc_ids):
 
 @torch.no_grad()
 def hybrid_search(model, dense_index, sparse_index, row_off, claims, k, device,
-                  bigram_only=False):
+                  bigram_only=False, method="gather"):
     """Sparse filter, dense rerank for a batch of claims (src/evaluation.py:57-83 feeding
     :110-112), all on the device: the claims' candidate columns (SparseIndex.candidates)
     expanded to their evidence rows (``row_off``, int64 [n_cols + 1] on the device) and
     each claim's ``ctx2vec`` embedding ranked against its own rows only.  Returns
-    (scores [Q, k], idx [Q, k] corpus rows, n [Q]) as rerank_topk."""
+    (scores [Q, k], idx [Q, k] corpus rows, n [Q]) as rerank_topk.  ``method``: "gather",
+    "stream" or "auto" (``ShardedDenseIndex.search_candidates``); the row lists are
+    ascending by construction, which the stream method needs."""
     from irc_amd.retrieval import expand_ranges
 
     q = model.ctx2vec(claims, device)
     cand, off = sparse_index.candidates(claims, bigram_only)
     rows, rows_off = expand_ranges(cand, off, row_off)
-    return dense_index.search_candidates(q, rows, rows_off, k)
+    return dense_index.search_candidates(q, rows, rows_off, k, method=method, ascending=True)
 
 
 @torch.no_grad()
@@ -189,7 +191,8 @@ def predict_hybrid(args, k=100):
     """The reference's two-stage predict: per claim batch the hashed n-gram filter, then
     the bi-encoder's exact top-k over the filter's candidates only.  Prints each batch's
     latency and the evidence recall@k (a claim with no candidates is a miss); returns
-    recall@k.  Single process."""
+    recall@k.  Single process.  ``args.rerank_method`` (default "auto") picks the scoring
+    method per batch; the ranking contract is the same either way."""
     assert args.ckpt is not None
     if getattr(args, "dist_group", None) is not None and int(getattr(args, "world_size", 1)) > 1:
         raise NotImplementedError("--retrieval hybrid runs in a single process: the collective "
@@ -206,11 +209,13 @@ def predict_hybrid(args, k=100):
     titles, texts, row_off = hybrid_corpus(loader.dataset.wiki, metadata["doc_dict"][1])
     row_off = torch.tensor(row_off, dtype=torch.int64, device=args.device)
     index = ShardedDenseIndex(encode_corpus(model, texts, args.device))
+    method = getattr(args, "rerank_method", "auto")  # main.py --rerank-method
     hits = total = 0
     for batch in tqdm(loader, desc="Iteration"):
         claims = [d["claim"] for d in batch]
         s = time.time()
-        _, idx, _ = hybrid_search(model, index, sparse_index, row_off, claims, k, args.device)
+        _, idx, _ = hybrid_search(model, index, sparse_index, row_off, claims, k, args.device,
+                                  method=method)
         torch.cuda.synchronize()
         print(f"batch of {len(claims)} claims: {time.time() - s:.4f}s")
         for d, row in zip(batch, idx.cpu().tolist()):

@@ -1,7 +1,9 @@
-"""Candidate-restricted top-k against the full scan: where the two cross.
+"""Candidate-restricted top-k, gathered and streamed, against the full scan: where they
+cross.
 
     python tools/rerank_probe.py [--n 250000] [--d 768] [--k 100] [--rounds 10] [--sets 4]
     python tools/rerank_probe.py --tables profiles/rerank_probe.json   # the documents' tables
+    python tools/rerank_probe.py --tables profiles/rerank_stream_probe.json  # + stream table
 
 One MI355X, the C3 shard (250k x 768 bf16, larger than the Infinity Cache), random
 ascending candidate lists of 0.1 / 1 / 5 / 25 % of the shard per query, Q in {1, 16, 64,
@@ -12,6 +14,10 @@ process (median over the rounds); the rerank calls of a window cycle through `se
 independent draws of the lists, as a serving loop's batches would bring new lists; then, in a separate profiled pass, the scoring and select kernels' own times
 (the library's per-launch events) and the scoring pass's achieved bytes/s, n_cand * D * 2
 over its time, beside the 5.5-5.8 TB/s whole-row gather rate of 1,152-2,304-byte rows.
+The streamed method (rerank_topk(method="stream", ascending=True)) is a third party to the
+same alternation -- same windows, same list draws -- with its own profiled pass
+(rerank_stream_score, rerank_select) and a gather-against-stream crossover per Q
+(``crossover_frac_stream``, the constants of retrieval.rerank_method).
 Prints a table to stderr and ONE JSON line to stdout."""
 import argparse
 import ctypes
@@ -45,12 +51,63 @@ def _prof(lib, name):
     return tot.value * 1e3 / n, work.value / n  # us per launch, work per launch
 
 
+def _crossover(rows, num, den):
+    """Candidate fraction where rows[num] / rows[den] passes 1, log-log interpolated between
+    the two measured fractions that bracket it; "< f" / "> f" when it never does."""
+    import math
+
+    row = sorted(rows, key=lambda c: c["frac"])
+    r = [math.log(c[num] / c[den]) for c in row]
+    val = None
+    if r and r[0] > 0:
+        val = f"< {row[0]['frac']}"
+    elif r and r[-1] < 0:
+        val = f"> {row[-1]['frac']}"
+    for a, b, ra, rb in zip(row, row[1:], r, r[1:]):
+        if ra <= 0 < rb:
+            w = -ra / (rb - ra)
+            val = math.exp(math.log(a["frac"]) + w * (math.log(b["frac"]) - math.log(a["frac"])))
+    return val
+
+
+def stream_tables(r):
+    """The stream method's table of DESIGN.md 6e: per cell the stream call, the share of
+    it that is the select kernel, and its ratio to the design's floor, scan call + select
+    kernel."""
+    cells = r["cells"]
+    print("| Q | candidates / query | gather call | stream call | pick kernels | "
+          "select kernel | select share | scan call | stream / (scan + select) |\n"
+          "|---|---|---|---|---|---|---|---|---|")
+    for c in cells:
+        print(f"| {c['Q']} | {c['cand_per_query']:,} ({100 * c['frac']:g}%) | "
+              f"{c['rerank_call_us']:,.1f} | {c['stream_call_us']:,.1f} | "
+              f"{c['stream_score_kernel_us']:,.1f} | {c['stream_select_kernel_us']:.1f} | "
+              f"{100 * c['stream_select_share']:.0f}% | {c['scan_call_us']:.1f} | "
+              f"{c['stream_over_floor']:.2f} |")
+    print()
+    qs = sorted({c["Q"] for c in cells})
+    print("    candidates per query  " + "".join(f"{'Q = ' + str(q):>18}" for q in qs))
+    for frac in sorted({c["frac"] for c in cells}):
+        row = {c["Q"]: c for c in cells if c["frac"] == frac}
+        n = next(iter(row.values()))["cand_per_query"]
+        print(f"    {n:>8,} ({100 * frac:g} %)".ljust(26) + "".join(
+            f"{row[q]['rerank_call_us']:>9,.0f} / {row[q]['stream_call_us']:<6,.0f}" for q in qs))
+    print()
+    print("gather-against-stream crossover:", r["crossover_frac_stream"])
+    worst = max(cells, key=lambda c: c["spread_pct"]["stream"])
+    print(f"largest min-max spread of the stream windows: {worst['spread_pct']['stream']:.2f}% "
+          f"(Q = {worst['Q']}, {100 * worst['frac']:g}%); rounds per cell: {r['rounds']}")
+    print()
+
+
 def tables(path):
     """The tables of DESIGN.md 6e and of the search_candidates docstring, from a recorded
     JSON line (no device needed): what the documents quote is what the file holds."""
     with open(path) as f:
         r = json.load(f)
     cells = r["cells"]
+    if "crossover_frac_stream" in r:
+        stream_tables(r)
     print("| Q | candidates / query | rerank call | scoring kernel | scoring TB/s | "
           "select kernel | scan call |\n|---|---|---|---|---|---|---|")
     for c in cells:
@@ -124,8 +181,15 @@ def main():
                 turn[0] += 1
                 return retrieval.rerank_topk(qq, docs, cands[turn[0] % args.sets], off, args.k)
 
+            sturn = [0]
+
+            def stm():
+                sturn[0] += 1
+                return retrieval.rerank_topk(qq, docs, cands[sturn[0] % args.sets], off, args.k,
+                                             method="stream", ascending=True)
+
             est = {}
-            for name, fn in (("rerank", rer), ("scan", scan)):
+            for name, fn in (("rerank", rer), ("stream", stm), ("scan", scan)):
                 for _ in range(3):
                     fn()
                 torch.cuda.synchronize()
@@ -133,9 +197,11 @@ def main():
             reps = {m: max(2 * args.sets, min(4000, int(args.window_ms / max(est[m], 1e-3))))
                     for m in est}
             reps["rerank"] -= reps["rerank"] % args.sets  # every draw equally often
-            t = {"rerank": [], "scan": []}
-            for _ in range(args.rounds):  # alternate the two
+            reps["stream"] -= reps["stream"] % args.sets
+            t = {"rerank": [], "stream": [], "scan": []}
+            for _ in range(args.rounds):  # alternate the three
                 t["rerank"].append(_window_ms(rer, reps["rerank"]))
+                t["stream"].append(_window_ms(stm, reps["stream"]))
                 t["scan"].append(_window_ms(scan, reps["scan"]))
             # kernel times in a pass of their own (per-launch events slow the host)
             lib.irc_prof_reset()
@@ -146,6 +212,16 @@ def main():
             lib.irc_prof_enable(0)
             score_us, score_bytes = _prof(lib, b"rerank_score")
             select_us, _ = _prof(lib, b"rerank_select")
+            lib.irc_prof_reset()
+            lib.irc_prof_enable(1)
+            for _ in range(min(reps["stream"], 12 * args.sets)):
+                stm()
+            torch.cuda.synchronize()
+            lib.irc_prof_enable(0)
+            pick_us, _ = _prof(lib, b"rerank_stream_score")
+            sselect_us, _ = _prof(lib, b"rerank_select")
+            stream_us = statistics.median(t["stream"]) * 1e3
+            scan_us = statistics.median(t["scan"]) * 1e3
             cell = {
                 "Q": Q, "frac": frac, "cand_per_query": n, "n_cand": Q * n,
                 "rerank_call_us": statistics.median(t["rerank"]) * 1e3,
@@ -154,6 +230,13 @@ def main():
                 "scan_call_us_minmax": [min(t["scan"]) * 1e3, max(t["scan"]) * 1e3],
                 "score_kernel_us": score_us, "select_kernel_us": select_us,
                 "score_bytes": score_bytes,
+                "stream_call_us": stream_us,
+                "stream_call_us_minmax": [min(t["stream"]) * 1e3, max(t["stream"]) * 1e3],
+                # the foreign-key and pick kernels, timed as one span
+                "stream_score_kernel_us": pick_us, "stream_select_kernel_us": sselect_us,
+                "stream_select_share": sselect_us / stream_us,
+                # the floor of the design: a full scan's call plus the select over the keys
+                "stream_over_floor": stream_us / (scan_us + sselect_us),
                 "score_TBps": score_bytes / (score_us * 1e-6) / 1e12 if score_us else None,
                 "reps": reps,
                 "spread_pct": {m: 100.0 * (max(t[m]) - min(t[m])) / statistics.median(t[m])
@@ -162,31 +245,20 @@ def main():
             cells.append(cell)
             print(f"Q={Q:4d} frac={frac:6.3f} n_cand={Q * n:9d}  rerank {cell['rerank_call_us']:9.1f} us"
                   f"  (score {score_us:9.1f} us, {cell['score_TBps'] or 0:5.2f} TB/s; select "
-                  f"{select_us:7.1f} us)  scan {cell['scan_call_us']:8.1f} us", file=sys.stderr,
-                  flush=True)
-    # candidate fraction where the two call times cross, per Q: log-log interpolation
-    # between the two measured fractions that bracket it
-    import math
-
-    cross = {}
+                  f"{select_us:7.1f} us)  scan {cell['scan_call_us']:8.1f} us  stream "
+                  f"{stream_us:9.1f} us (pick {pick_us:8.1f} us, select {sselect_us:7.1f} us)",
+                  file=sys.stderr, flush=True)
+    # candidate fraction where two call times cross, per Q (_crossover)
+    cross, cross_stream = {}, {}
     for Q in args.q:
-        row = sorted((c for c in cells if c["Q"] == Q), key=lambda c: c["frac"])
-        r = [math.log(c["rerank_call_us"] / c["scan_call_us"]) for c in row]
-        val = None
-        if r and r[0] > 0:
-            val = f"< {row[0]['frac']}"
-        elif r and r[-1] < 0:
-            val = f"> {row[-1]['frac']}"
-        for a, b, ra, rb in zip(row, row[1:], r, r[1:]):
-            if ra <= 0 < rb:
-                w = -ra / (rb - ra)
-                val = math.exp(math.log(a["frac"]) + w * (math.log(b["frac"]) - math.log(a["frac"])))
-        cross[str(Q)] = val
-    print(json.dumps({"probe": "rerank_vs_scan", "device": torch.cuda.get_device_name(0),
+        row = [c for c in cells if c["Q"] == Q]
+        cross[str(Q)] = _crossover(row, "rerank_call_us", "scan_call_us")
+        cross_stream[str(Q)] = _crossover(row, "rerank_call_us", "stream_call_us")
+    print(json.dumps({"probe": "rerank_gather_stream_scan", "device": torch.cuda.get_device_name(0),
                       "N": args.n, "D": args.d, "k": args.k, "rounds": args.rounds,
                       "window_ms": args.window_ms, "sets": args.sets,
                       "gather_guide_TBps": list(GATHER_TBS), "cells": cells,
-                      "crossover_frac": cross}))
+                      "crossover_frac": cross, "crossover_frac_stream": cross_stream}))
 
 
 if __name__ == "__main__":
