@@ -251,6 +251,11 @@ int irc_gemm_ln(int epilogue, int64_t M, int64_t N, int64_t K, const void* A, in
  * previous setting. */
 int irc_gemm_set_big_mf16(int on);
 
+/* The ping-pong 256 x 256 bf16 GEMM path: 1 = on (the default, or what IRC_GEMM_PP set),
+ * 0 = off, so every bf16 launch goes to the big-tile or the general kernel (tests and A/B
+ * runs).  Returns the previous setting. */
+int irc_gemm_set_pp(int on);
+
 /* ------------------------------------------------------------- BERT encoder
  * Frozen BERT forward pieces (contrastive_module.py:36-41 -> HF BertModel):
  * fused embedding gather + LayerNorm, LayerNorm (residual fused in the GEMM),

@@ -27,6 +27,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 // Grouped output-tile order of the GEMM kernels' tiles (see gemm_group_m; 0 = row-major).
 #ifndef IRC_GEMM_GROUP_M
@@ -590,6 +591,178 @@ inline std::atomic<int>& big_mf16_mode() {
 }
 inline bool big_mf16() { return big_mf16_mode().load(std::memory_order_relaxed) != 0; }
 
+// The staged epilogue of the default big-tile form (16x16x32 accumulators, bf16 C, 16-byte
+// aligned rows): the arithmetic of gemm_big_kernel's general staged epilogue, operation for
+// operation, with less around it.  The tile runs with the matrix pipe idle and nothing to
+// overlap, so its instruction count is launch time.
+//  - First stage: elements e, e + 1 of an accumulator share a column, hence bias and alpha;
+//    they go through one packed FMA and gelu_lite2 as a pair.
+//  - Second stage: a lane's chunks sit at the same (row, column) of each 32-row pass --
+//    chunk c = 64 it + lane, and 64 NB chunks are RSTEP whole rows, so iteration it is base
+//    chunk it % NB moved down (it / NB) RSTEP rows.  The NB LDS and C / R byte offsets are
+//    computed once; interior tiles (uniform test) store through a uniform row-block base
+//    plus those 32-bit offsets, without predicates, and read the residual one pass ahead;
+//    edge tiles keep predicates and 64-bit addresses.
+template <int EPI, int WNB>
+__device__ __forceinline__ void big_epilogue_bf16(const Args& g, const f32x4 (&acc4)[8][2 * WNB],
+                                                  char* lds, unsigned short* C,
+                                                  const unsigned short* R, const float* bias,
+                                                  int m0, int n0, int wave, int lane) {
+  constexpr int BN = 128 * WNB, WCOLS = 32 * WNB, PITCH = WCOLS + 8;
+  constexpr int CPR = WCOLS / 8;           // 16-byte bf16 chunks per row
+  constexpr int NCH = 32 * CPR / 64;       // chunks per lane per pass
+  constexpr int NB = CPR == 12 ? 3 : 1;    // base chunks
+  constexpr int RSTEP = 64 * NB / CPR;     // rows between repeats of a base chunk
+  static_assert(64 * NB % CPR == 0 && NCH % NB == 0, "the chunk map repeats every NB iterations");
+  constexpr bool READS_R = EPI == EPI_BIAS_RESID || EPI == EPI_RESID || EPI == EPI_DGELU;
+  constexpr bool USES_R = READS_R || EPI == EPI_BIAS_GELU_SAVE;
+  const int wm = wave >> 2, wn = wave & 3;
+  float* st = reinterpret_cast<float*>(lds) + wave * (32 * PITCH);
+  const int rbase0 = m0 + wm * 128;
+  const int cbase = n0 + wn * WCOLS;
+  // 32-bit byte offsets below: 32 rows of C / R
+  const bool fast = m0 + big::BM <= g.M && n0 + BN <= g.N && g.ldc < (1 << 24) &&
+                    (!USES_R || g.ldr < (1 << 24));
+  float bv[2 * WNB];
+#pragma unroll
+  for (int j = 0; j < 2 * WNB; ++j) {
+    const int col = cbase + j * 16 + (lane & 15);
+    bv[j] = epi_has_bias(EPI) && col < g.N ? bias[col] : 0.f;
+  }
+  const f32x2_t alpha = {g.alpha, g.alpha};
+  float* sw = st + 4 * (lane >> 4) * PITCH + (lane & 15);
+
+  // one chunk: residual / GELU backward / pre-activation save, then round to bf16
+  auto finish = [&](const f32x4& v0, const f32x4& v1, const u16x8& rr,
+                    const unsigned short* rp) -> u16x8 {
+    float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+    if constexpr (READS_R) {
+#pragma unroll
+      for (int t = 0; t < 8; ++t)
+        v[t] = EPI == EPI_DGELU ? v[t] * gelu_grad_fast(bf16_to_f32(rr[t]))
+                                : v[t] + bf16_to_f32(rr[t]);
+    }
+    if constexpr (EPI == EPI_BIAS_GELU_SAVE) {
+      u16x8 pre;
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        pre[t] = f32_to_bf16(v[t]);
+        v[t] = gelu_fast(v[t]);
+      }
+      *reinterpret_cast<u16x8*>(const_cast<unsigned short*>(rp)) = pre;
+    }
+    u16x8 o;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) o[t] = f32_to_bf16(v[t]);
+    return o;
+  };
+  // The base chunks' LDS index and C / R byte offsets.  Set when pass 0 is staged and its
+  // accumulators are dead (the lane id goes through an opaque copy, so the compiler cannot
+  // compute them earlier): before that the registers are full.
+  uint32_t soff[NB], coff[NB], roff[NB];
+  auto set_offsets = [&]() {
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      const int c = b * 64 + ln;
+      const int rl = c / CPR, c8 = (c % CPR) * 8;
+      soff[b] = rl * PITCH + c8;
+      coff[b] = 2u * (uint32_t)(rl * (int)g.ldc + c8);
+      roff[b] = USES_R ? 2u * (uint32_t)(rl * (int)g.ldr + c8) : 0u;
+    }
+  };
+  // Interior tiles read a pass's residual chunks one pass ahead: chunk it of pass i + 1 is
+  // requested as soon as chunk it of pass i is used (pass 0's when its second stage
+  // begins: the accumulators fill the registers until then), so its latency runs under
+  // the rest of the pass and the next first stage.  Loaded where they are used, each
+  // chunk waits for its load and for the store before it (one counter): 24 round trips
+  // in a row per wave.
+  u16x8 rq[NCH];
+  auto load_r = [&](int pass, int it) {
+    const char* ru = reinterpret_cast<const char*>(R + (int64_t)(rbase0 + pass * 32) * g.ldr + cbase);
+    rq[it] = *reinterpret_cast<const u16x8*>(ru + 2 * ((it / NB) * RSTEP) * g.ldr + roff[it % NB]);
+  };
+
+  // the four passes, once per kind of tile: one uniform branch, and neither kind keeps the
+  // other's addresses in registers
+  auto passes = [&](auto fast_c) {
+  constexpr bool FAST = decltype(fast_c)::value;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+    for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+      for (int j = 0; j < 2 * WNB; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; e += 2) {
+          const f32x4& a = acc4[2 * i + ii][j];
+          f32x2_t v = __builtin_elementwise_fma(f32x2_t{a[e], a[e + 1]}, alpha, f32x2_t{bv[j], bv[j]});
+          if constexpr (EPI == EPI_BIAS_GELU) v = gelu_lite2(v);
+          sw[(16 * ii + e) * PITCH + j * 16] = v.x;
+          sw[(16 * ii + e + 1) * PITCH + j * 16] = v.y;
+        }
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const int rbase = rbase0 + i * 32;
+    if constexpr (FAST) {
+      // uniform: this pass's first row, the wave's first column
+      char* cu = reinterpret_cast<char*>(C + (int64_t)rbase * g.ldc + cbase);
+      const char* ru = USES_R ? reinterpret_cast<const char*>(R + (int64_t)rbase * g.ldr + cbase)
+                              : nullptr;
+      if (i == 0) {
+        set_offsets();
+        if constexpr (READS_R) {
+#pragma unroll
+          for (int it = 0; it < NCH; ++it) load_r(0, it);
+        }
+      }
+#pragma unroll
+      for (int it = 0; it < NCH; ++it) {
+        const int b = it % NB, ra = (it / NB) * RSTEP;
+        const float* sp = st + soff[b] + ra * PITCH;
+        const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp);
+        const f32x4 v1 = *reinterpret_cast<const f32x4*>(sp + 4);
+        const u16x8 o = finish(
+            v0, v1, rq[it],
+            reinterpret_cast<const unsigned short*>(ru + 2 * ra * g.ldr + roff[b]));
+#ifdef IRC_PP_DIAG_NOSTORE  // diagnostic build: the epilogue without its C stores
+        if (o[0] == 0x7fc1 && o[7] == 0x7fc3)
+#endif
+        *reinterpret_cast<u16x8*>(cu + 2 * ra * g.ldc + coff[b]) = o;
+        if constexpr (READS_R) {
+          if (i < 3) load_r(i + 1, it);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int it = 0; it < NCH; ++it) {
+        const int c = it * 64 + lane;
+        const int rl = c / CPR, c8 = (c % CPR) * 8;
+        const int row = rbase + rl, col = cbase + c8;
+        if (row >= g.M || col >= g.N) continue;
+        const f32x4 v0 = *reinterpret_cast<const f32x4*>(&st[rl * PITCH + c8]);
+        const f32x4 v1 = *reinterpret_cast<const f32x4*>(&st[rl * PITCH + c8 + 4]);
+        const unsigned short* rp = USES_R ? R + (int64_t)row * g.ldr + col : nullptr;
+        u16x8 rr = {};
+        if constexpr (READS_R) rr = *reinterpret_cast<const u16x8*>(rp);
+        const u16x8 o = finish(v0, v1, rr, rp);
+#ifdef IRC_PP_DIAG_NOSTORE
+        if (o[0] == 0x7fc1 && o[7] == 0x7fc3)
+#endif
+        *reinterpret_cast<u16x8*>(C + (int64_t)row * g.ldc + col) = o;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
+  };
+  if (fast)
+    passes(std::true_type{});
+  else
+    passes(std::false_type{});
+}
+
 // MF16: v_mfma_f32_16x16x32_bf16 instead of 32x32x16 (2-slot form only): the same
 // 256 x 128 WNB tile and LDS image, 8 x 2 WNB accumulators of 16 x 16 per wave, one
 // k32 step per half K-tile.  The chunk key (r >> 1) & 7 stays conflict free for the
@@ -753,7 +926,14 @@ __global__ __launch_bounds__(big::NT, 1) void gemm_big_kernel(Args g) {
   const float* bias = g.bias ? g.bias + batch * g.sBias : nullptr;
   const TO* R = g.R ? reinterpret_cast<const TO*>(g.R) + batch * g.sR : nullptr;
   constexpr int WCOLS = 32 * WNB;  // columns per wave
-  if (g.vec_c) {
+  if constexpr (MF16 && sizeof(TO) == 2 && !LN) {
+    if (g.vec_c) {  // the default path: the same staged epilogue, trimmed (big_epilogue_bf16)
+      big_epilogue_bf16<EPI, WNB>(g, acc4, lds, reinterpret_cast<unsigned short*>(C),
+                                  reinterpret_cast<const unsigned short*>(R), bias, m0, n0, wave,
+                                  lane);
+      return;
+    }
+  } else if (g.vec_c) {
     // Staged epilogue: the wave's 128 x WCOLS fp32 tile goes through LDS in four
     // 32-row passes (row pitch WCOLS+8 floats: rows r and r+4 of the two
     // half-waves land 128 B apart in bank space, so the ds_write_b32 are
@@ -1091,6 +1271,7 @@ __global__ __launch_bounds__(big::NT, 1) void qkv_attn_kernel(QaArgs g) {
     unsigned short* Tq = reinterpret_cast<unsigned short*>(lds);  // [256][TQ] one head
     float* mb = reinterpret_cast<float*>(lds + BM * TQ * 2) + 128 * wave;
     const int odd = lane & 1;
+    const uint32_t psel = odd ? 0x03020706u : 0x05040100u;  // see the slot form below
     const int nsq = min(spt, nseq - tm * spt);  // sequences in this tile
     const int nit = nsq * nj;                   // (sequence, query block) items per head
 #pragma unroll
@@ -1108,7 +1289,7 @@ __global__ __launch_bounds__(big::NT, 1) void qkv_attn_kernel(QaArgs g) {
           for (int e2 = 0; e2 < 2; ++e2) {
             const uint32_t w = pk[i][j][e2];
             const uint32_t x = (uint32_t)__builtin_amdgcn_mov_dpp((int)w, 0xB1, 0xF, 0xF, false);
-            const uint32_t v = odd ? ((x >> 16) | (w & 0xFFFF0000u)) : ((w & 0xFFFFu) | (x << 16));
+            const uint32_t v = __builtin_amdgcn_perm(x, w, psel);
             const int rl = 128 * wm + 16 * i + 4 * (lane >> 4) + 2 * e2 + odd;
             *reinterpret_cast<uint32_t*>(&Tq[rl * TQ + tc]) = v;
           }
@@ -1217,8 +1398,11 @@ __global__ __launch_bounds__(big::NT, 1) void qkv_attn_kernel(QaArgs g) {
     if (wm == hf) {  // this half's accumulators -> T [128][TP]
       // a lane holds rows (r, r + 1) of its column; swapping with the neighbour lane
       // (DPP quad_perm [1,0,3,2]) gives the even lane columns (c, c + 1) of row r and the
-      // odd lane those of row r + 1: one 4-byte store per pair instead of two 2-byte ones
+      // odd lane those of row r + 1: one 4-byte store per pair instead of two 2-byte ones.
+      // One v_perm_b32 merges own word w and neighbour's x (bytes 0-3 of w, 4-7 of x):
+      // even lanes (w & 0xFFFF) | (x << 16), odd lanes (x >> 16) | (w & 0xFFFF0000)
       const int odd = lane & 1;
+      const uint32_t psel = odd ? 0x03020706u : 0x05040100u;
 #pragma unroll
       for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -1227,7 +1411,7 @@ __global__ __launch_bounds__(big::NT, 1) void qkv_attn_kernel(QaArgs g) {
           for (int e2 = 0; e2 < 2; ++e2) {
             const uint32_t w = pk[i][j][e2];
             const uint32_t x = (uint32_t)__builtin_amdgcn_mov_dpp((int)w, 0xB1, 0xF, 0xF, false);
-            const uint32_t v = odd ? ((x >> 16) | (w & 0xFFFF0000u)) : ((w & 0xFFFFu) | (x << 16));
+            const uint32_t v = __builtin_amdgcn_perm(x, w, psel);
             const int rl = 16 * i + 4 * (lane >> 4) + 2 * e2 + odd;
             *reinterpret_cast<uint32_t*>(&T[rl * TP + wn * 32 * WNB + 16 * j + (lane & 14)]) = v;
           }
@@ -1456,14 +1640,18 @@ static int gemm_group_m(int64_t N, int64_t bn) {
   return (N + bn - 1) / bn >= 12 ? 8 : 0;
 }
 
-// IRC_GEMM_PP=0 disables the ping-pong path (A/B experiments; read once).
-static bool pp_enabled() {
-  static const bool on = [] {
+// IRC_GEMM_PP=0 disables the ping-pong path (A/B experiments; read once).  irc_gemm_set_pp
+// changes it at run time: the tests reach the big-tile kernel at shapes of a few hundred
+// tiles that way, where the dispatch prefers the 256 x 256 tile.
+static std::atomic<int>& pp_mode() {
+  static std::atomic<int> on{[] {
     const char* e = getenv("IRC_GEMM_PP");
-    return !(e && e[0] == '0');
-  }();
+    return !(e && e[0] == '0') ? 1 : 0;
+  }()};
   return on;
 }
+static bool pp_enabled() { return pp_mode().load(std::memory_order_relaxed) != 0; }
+extern "C" int irc_gemm_set_pp(int on) { return pp_mode().exchange(on ? 1 : 0); }
 
 constexpr int64_t SPLIT_BLOCKS_DEFAULT = 256;  // split-K budget: one wave of 256 x 256 blocks
 // max_blocks > 0: the split-K budget; < 0: a grid cap of -max_blocks workgroups on an

@@ -96,6 +96,13 @@ def gemm_set_big_mf16(on) -> int:
     return int(_lib.load().irc_gemm_set_big_mf16(1 if on else 0))
 
 
+def gemm_set_pp(on) -> int:
+    """The ping-pong 256x256 bf16 GEMM path (irc_gemm_set_pp): True = on (the default),
+    False = every bf16 launch goes to the big-tile or the general kernel.  Returns the
+    previous setting."""
+    return int(_lib.load().irc_gemm_set_pp(1 if on else 0))
+
+
 def gemm_set_persistent(mode) -> int:
     """Persistent tile loop of the 256x256 bf16 GEMM (irc_gemm_set_persistent): 0 off
     (the default), 1 / True dynamic tiles with the next tile's first K-tile prestaged
