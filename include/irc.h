@@ -250,6 +250,17 @@ int irc_gemm_ln(int epilogue, int64_t M, int64_t N, int64_t K, const void* A, in
  * within a k32 step differs, so results agree within fp32 reassociation.  Returns the
  * previous setting. */
 int irc_gemm_set_big_mf16(int on);
+/* Operand staging of that loop (and of irc_qkv_attention's): 1 = buffer-addressed LDS-DMA
+ * (the default: one 32-bit lane offset per operand, the per-pass and per-K-tile parts of
+ * the address in scalar registers), 0 = a 64-bit address per lane and 16-byte piece,
+ * rebuilt every K-tile.  Tiles with clamped rows, and launches irc_gemm_big_dma_fits
+ * refuses, use the second form in either setting.  Same LDS image, so results are
+ * bit-identical.  Returns the previous setting. */
+int irc_gemm_set_big_dma(int on);
+/* Host-only query: 1 if both operands (A [M][K] with row stride lda, B [N][K] with row
+ * stride ldb, bf16) span less than 2^31 bytes, so that every byte offset of the
+ * buffer-addressed staging fits 31 bits; else 0. */
+int irc_gemm_big_dma_fits(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb);
 
 /* The ping-pong 256 x 256 bf16 GEMM path: 1 = on (the default, or what IRC_GEMM_PP set),
  * 0 = off, so every bf16 launch goes to the big-tile or the general kernel (tests and A/B

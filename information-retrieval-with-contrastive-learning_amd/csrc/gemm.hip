@@ -73,6 +73,7 @@ struct Args {
   float* P;          // split-K partials [batch][split][M][N] (raw sums), or null
   int group_m;       // big-tile kernel: grouped tile order (irc_common.h); 0 = row-major
   LnArgs ln;         // LayerNorm fold (big-tile kernel, bf16 C, vectorised epilogue)
+  int big_dma;       // big-tile 16x16x32 loop: buffer-addressed staging allowed (launch_big)
 };
 
 // bf16 K-outer (COL / KN) slabs are kept k-major in LDS: [BK=32 k][128 rows]
@@ -402,7 +403,8 @@ inline int split_count(int TIbytes, int out_f32, int epi, int64_t M, int64_t N, 
 // 2(M) x 4(N), 128 x 32*WNB per wave = 4 x WNB blocks of v_mfma_f32_32x32x16_bf16.
 // WNB = 3 (256x384) when N % 384 == 0 -- every BERT-base N (768, 2304, 3072), so
 // M = 32768 gives whole waves of tiles over 256 CUs -- else WNB = 2 (256x256).
-// Both tiles move global -> LDS by global_load_lds_dwordx4 (no VGPR staging),
+// Both tiles move global -> LDS by 16-byte LDS-DMA (no VGPR staging; global_load_lds_dwordx4,
+// or buffer_load_dwordx4 ... lds on the 16x16x32 loop's interior tiles, big::stage_buf),
 // double buffered (2 x 80 KB at WNB=3): tile k+1 is in flight while tile k is
 // consumed.  LDS rows are 128 B (64 k); the 16-byte chunk c of row r is stored at
 // chunk c ^ ((r >> 1) & 7) (big::chunk_key) so the row-wise ds_read_b128 fragment reads
@@ -455,6 +457,39 @@ __device__ __forceinline__ void stage(const unsigned short* __restrict__ X, int6
     glds16(X + (int64_t)gr * ld + k0 + c * 8, lds_tile + (i * NW + wave) * 1024);
   }
 }
+// stage() for a tile with no clamped row, through a buffer descriptor (blds16).  Pass i of
+// a lane addresses tile row row_0 + 64 i, row_0 = 8 wave + (lane >> 3), and 64 rows on the
+// chunk key (row >> 1) & 7 is the same, so the source splits into
+//   lane part (one VGPR for the whole K loop, dma_lane_off):
+//     row_0 ld 2 + ((lane & 7) ^ chunk_key(row_0)) 16
+//   uniform part (SGPRs): soff + i pass_bytes, soff = (tile's first row) ld 2 + k0 2,
+//     pass_bytes = 64 ld 2
+// and the LDS image is stage()'s byte for byte.  The sequence-slot layout with slots of 64
+// rows is affine too: pass i is sequence (r0 >> 6) + i, so the lane's row is token
+// min(row_0, ls - 1), the tile's first row (r0 >> 6) ls and pass_bytes = ls ld 2.  (Slots
+// of 128 rows clamp differently in odd and even passes and stay on stage().)
+template <int ROWS>
+__device__ __forceinline__ void stage_buf(__amdgpu_buffer_rsrc_t rsrc, uint32_t lane_off,
+                                          uint32_t soff, uint32_t pass_bytes, char* lds_tile,
+                                          int wave) {
+  constexpr int PASSES = ROWS * 8 / NT;
+#pragma unroll
+  for (int i = 0; i < PASSES; ++i)
+    blds16(rsrc, lane_off, soff + i * pass_bytes, lds_tile + (i * NW + wave) * 1024);
+}
+__device__ __forceinline__ uint32_t dma_lane_off(int64_t ld, int wave, int lane, int ls = 0) {
+  const int row0 = 8 * wave + (lane >> 3);
+  const int gr = ls == 0 ? row0 : min(row0, ls - 1);
+  return (uint32_t)gr * (uint32_t)ld * 2u + (uint32_t)(((lane & 7) ^ chunk_key(row0)) * 16);
+}
+// Host-side gate of the buffer form for one operand of `rows` rows of K elements, row
+// stride ld: the descriptor spans the whole operand and every byte offset a tile can
+// form (below the span) fits 31 bits.
+inline bool dma_fits(int64_t rows, int64_t K, int64_t ld) {
+  if (rows <= 0 || K <= 0 || ld < 0 || ld > (1ll << 31)) return false;
+  return ((rows - 1) * ld + K) * 2 < (1ll << 31);
+}
+
 // Ring form (RING = true): 32-deep K-tiles in 4 LDS slots (64-byte rows, 40 KB a
 // slot at 256 x 384), three in flight: K-tile kt + 3 is issued into the slot K-tile
 // kt - 1 used, right after the one barrier of iteration kt (every wave is past its
@@ -515,14 +550,33 @@ template <int WNB>
 __device__ __forceinline__ void mainloop_mf16(const unsigned short* A, int64_t lda,
                                               const unsigned short* B, int64_t ldb, int m0,
                                               int n0, int M, int N, int K, char* lds, int wave,
-                                              int lane, f32x4 (&acc4)[8][2 * WNB], int ls = 0,
-                                              int sh = 6) {
+                                              int lane, f32x4 (&acc4)[8][2 * WNB], bool dma,
+                                              int ls = 0, int sh = 6) {
   constexpr int BN = 128 * WNB;
   constexpr int A_BYTES = BM * ROW_BYTES, STAGE = A_BYTES + BN * ROW_BYTES;
   const int wm = wave >> 2, wn = wave & 3;
   const int nk = K / BK;
-  stage<BM>(A, lda, m0, M, 0, lds, wave, lane, ls, sh);
-  stage<BN>(B, ldb, n0, N, 0, lds + A_BYTES, wave, lane);
+  // Interior tiles of a launch that passed the host's gate (dma; dma_fits) stage through
+  // stage_buf: descriptors over the whole operands, one lane offset each for the whole
+  // loop, everything that moves with the pass and the K-tile in SGPRs.  Uniform test.
+  const int a_rows = ls == 0 ? 64 : ls;                 // operand rows between two passes
+  const int a_row0 = ls == 0 ? m0 : (m0 >> sh) * ls;    // the tile's first operand row
+  const bool buf = dma && (ls == 0 || sh == 6) && a_row0 + (BM / 64) * a_rows <= M && n0 + BN <= N;
+  const __amdgpu_buffer_rsrc_t ra = buffer_rsrc(A, (uint32_t)(((int64_t)(M - 1) * lda + K) * 2));
+  const __amdgpu_buffer_rsrc_t rb = buffer_rsrc(B, (uint32_t)(((int64_t)(N - 1) * ldb + K) * 2));
+  const uint32_t a_pass = (uint32_t)a_rows * (uint32_t)lda * 2u, b_pass = 128u * (uint32_t)ldb;
+  const uint32_t a_tile = (uint32_t)a_row0 * (uint32_t)lda * 2u;
+  const uint32_t b_tile = (uint32_t)n0 * (uint32_t)ldb * 2u;
+  uint32_t a_lane = 0, b_lane = 0;
+  if (buf) {
+    a_lane = dma_lane_off(lda, wave, lane, ls);
+    b_lane = dma_lane_off(ldb, wave, lane);
+    stage_buf<BM>(ra, a_lane, a_tile, a_pass, lds, wave);
+    stage_buf<BN>(rb, b_lane, b_tile, b_pass, lds + A_BYTES, wave);
+  } else {
+    stage<BM>(A, lda, m0, M, 0, lds, wave, lane, ls, sh);
+    stage<BN>(B, ldb, n0, N, 0, lds + A_BYTES, wave, lane);
+  }
   wait_vmcnt<0>();
   __syncthreads();
   const int l16 = lane & 15, q4 = lane >> 4;
@@ -536,9 +590,14 @@ __device__ __forceinline__ void mainloop_mf16(const unsigned short* A, int64_t l
 #endif
     BSTAMP(kt, 0);
     char* nxt = lds + (cur ^ 1) * STAGE;
-    if (more) {
-      // the DMA addresses are re-derived per K-tile (kept live through the loop they
-      // would push the 16x16 fragments into spills)
+    if (more && buf) {
+      const uint32_t kb = (uint32_t)(kt + 1) * ROW_BYTES;
+      stage_buf<BM>(ra, a_lane, a_tile + kb, a_pass, nxt, wave);
+      stage_buf<BN>(rb, b_lane, b_tile + kb, b_pass, nxt + A_BYTES, wave);
+    } else if (more) {
+      // edge tiles and launches outside the gate: the 64-bit DMA addresses are re-derived
+      // per K-tile (kept live through the loop they would push the 16x16 fragments into
+      // spills)
       int ln = lane;
       asm volatile("" : "+v"(ln));
       stage<BM>(A, lda, m0, M, (kt + 1) * BK, nxt, wave, ln, ls, sh);
@@ -590,6 +649,18 @@ inline std::atomic<int>& big_mf16_mode() {
   return on;
 }
 inline bool big_mf16() { return big_mf16_mode().load(std::memory_order_relaxed) != 0; }
+
+// Buffer-addressed staging in the 16x16x32 loop (big::stage_buf): on by default,
+// irc_gemm_set_big_dma switches it at run time (the tests compare both bit for bit).  A
+// launch takes it when both operands pass big::dma_fits.
+inline std::atomic<int>& big_dma_mode() {
+  static std::atomic<int> on{1};
+  return on;
+}
+inline int big_dma_flag(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb) {
+  return big_dma_mode().load(std::memory_order_relaxed) != 0 && big::dma_fits(M, K, lda) &&
+         big::dma_fits(N, K, ldb);
+}
 
 // The staged epilogue of the default big-tile form (16x16x32 accumulators, bf16 C, 16-byte
 // aligned rows): the arithmetic of gemm_big_kernel's general staged epilogue, operation for
@@ -861,7 +932,8 @@ __global__ __launch_bounds__(big::NT, 1) void gemm_big_kernel(Args g) {
     }
     __syncthreads();  // the epilogue's staging rows overlap the ring
   } else if constexpr (MF16) {
-    big::mainloop_mf16<WNB>(A, g.lda, B, g.ldb, m0, n0, g.M, g.N, g.K, lds, wave, lane, acc4);
+    big::mainloop_mf16<WNB>(A, g.lda, B, g.ldb, m0, n0, g.M, g.N, g.K, lds, wave, lane, acc4,
+                            g.big_dma != 0);
   } else {
   const int nk = g.K / BK;
   big::stage<BM>(A, g.lda, m0, g.M, 0, lds, wave, lane);
@@ -1190,6 +1262,7 @@ struct QaArgs {
   float scale;
   int L;                    // sequence length, 1..128
   int group_m;              // grouped tile order (grouped_tile; 0 = row-major)
+  int big_dma;              // buffer-addressed staging allowed (see gemm::Args)
 };
 
 //
@@ -1237,7 +1310,7 @@ __global__ __launch_bounds__(big::NT, 1) void qkv_attn_kernel(QaArgs g) {
 #pragma unroll
     for (int j = 0; j < 2 * WNB; ++j) acc4[i][j] = (f32x4)0.0f;
   big::mainloop_mf16<WNB>(g.x, g.ldx, g.w, g.K, m0, n0, g.M, 3 * g.H, g.K, lds, wave, lane, acc4,
-                          ls, SH);
+                          g.big_dma != 0, ls, SH);
 
   unsigned short* T = reinterpret_cast<unsigned short*>(lds);    // [128][TP] staged half
   float* mbw = reinterpret_cast<float*>(lds + 128 * TP * 2) + SL * wave;  // this wave's key bias
@@ -1538,7 +1611,9 @@ inline int big_wnb(const Args& g, int batch, int la, int lb) {
 }
 
 template <typename TO, int EPI, bool LN = false>
-static int launch_big(const Args& g, int batch, int wnb, hipStream_t st) {
+static int launch_big(const Args& g0, int batch, int wnb, hipStream_t st) {
+  Args g = g0;
+  g.big_dma = big_dma_flag(g.M, g.N, g.K, g.lda, g.ldb);
   const int bn = 128 * wnb;
   const int tiles = ((g.M + big::BM - 1) / big::BM) * ((g.N + bn - 1) / bn);
   prof_begin(st);
@@ -1760,7 +1835,7 @@ extern "C" int irc_qkv_attention(int64_t M, int64_t H, int64_t heads, int64_t L,
   IRC_REQUIRE(bias_perm != nullptr, "qkv_attention: bias required");
   QaArgs a{static_cast<const unsigned short*>(x), static_cast<const unsigned short*>(wqkv_perm),
            bias_perm, mask, static_cast<unsigned short*>(ctx), (int)M, (int)H, (int)H, ldx, ldc,
-           0.125f, (int)L, IRC_GEMM_GROUP_M};
+           0.125f, (int)L, IRC_GEMM_GROUP_M, big_dma_flag(M, 3 * H, H, ldx, H)};
   // Row-major tile order here even where Wqkv exceeds an XCD's 4 MB L2 (C4: 6 MB): grouped
   // (8 rows) measured 11.35-11.39k against 11.38-11.43k pairs/s on the C4 leg, GEMM traffic
   // 407 vs 415 MB per launch (profiles/r06_n/)
@@ -1805,6 +1880,18 @@ extern "C" int irc_big_dbg_stamps(uint64_t* out /* [64][5][2] */) {
 // previous setting.
 extern "C" int irc_gemm_set_big_mf16(int on) {
   return irc::gemm::big_mf16_mode().exchange(on ? 1 : 0);
+}
+
+// Buffer-addressed (1, the default) or per-lane 64-bit (0) LDS-DMA staging in the big-tile
+// kernel's 16x16x32 loop and in qkv_attn_kernel; returns the previous setting.
+extern "C" int irc_gemm_set_big_dma(int on) {
+  return irc::gemm::big_dma_mode().exchange(on ? 1 : 0);
+}
+
+// Host-only: whether a launch with these operands (A [M][K] stride lda, B [N][K] stride
+// ldb, bf16) passes the gate of the buffer-addressed staging.
+extern "C" int irc_gemm_big_dma_fits(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb) {
+  return irc::gemm::big::dma_fits(M, K, lda) && irc::gemm::big::dma_fits(N, K, ldb) ? 1 : 0;
 }
 
 // 4-slot ring (1) or 2-slot loop (0, the default: the ring measured no faster on

@@ -191,6 +191,22 @@ __device__ __forceinline__ void glds16_pol(const void* gsrc, void* lds_base) {
       (__attribute__((address_space(3))) void*)lds_base, 16, 0, AUX);
 }
 
+// The same DMA through a buffer descriptor (buffer_load_dwordx4 ... offen lds): the source
+// of lane l is the descriptor's base + voff (per lane, one VGPR) + soff (wave-uniform, an
+// SGPR), so a loop that only moves the uniform part does no vector address arithmetic.
+// Build the descriptor from wave-uniform values only (kernel arguments, block indices, a
+// readfirstlane'd wave index): otherwise the compiler wraps every load in a readfirstlane
+// loop.  A 16-byte piece that does not lie within the descriptor's num_records bytes
+// reads as zeros instead of faulting.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc(const void* base, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff,
+                                       void* lds_base) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_base,
+                                           16, (int)voff, (int)soff, 0, 0);
+}
+
 // Order-preserving map fp32 -> uint32 (larger float -> larger uint).  -0.0 is
 // folded to +0.0 and NaN to 0 (lowest), matching oracle.canon_scores.
 __device__ __forceinline__ uint32_t orderable_f32(float f) {

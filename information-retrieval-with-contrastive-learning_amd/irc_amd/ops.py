@@ -96,6 +96,19 @@ def gemm_set_big_mf16(on) -> int:
     return int(_lib.load().irc_gemm_set_big_mf16(1 if on else 0))
 
 
+def gemm_set_big_dma(on) -> int:
+    """Operand staging of the big-tile bf16 GEMM's 16x16x32 loop and of qkv_attention
+    (irc_gemm_set_big_dma): True = buffer-addressed LDS-DMA (the default), False = per-lane
+    64-bit addresses.  Bit-identical results.  Returns the previous setting."""
+    return int(_lib.load().irc_gemm_set_big_dma(1 if on else 0))
+
+
+def gemm_big_dma_fits(M, N, K, lda, ldb) -> bool:
+    """Whether bf16 operands A [M, K] (row stride lda) and B [N, K] (row stride ldb) pass
+    the host-side gate of the buffer-addressed staging (irc_gemm_big_dma_fits; no GPU)."""
+    return bool(_lib.load().irc_gemm_big_dma_fits(M, N, K, lda, ldb))
+
+
 def gemm_set_pp(on) -> int:
     """The ping-pong 256x256 bf16 GEMM path (irc_gemm_set_pp): True = on (the default),
     False = every bf16 launch goes to the big-tile or the general kernel.  Returns the
