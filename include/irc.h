@@ -131,6 +131,33 @@ int irc_rerank_topk_stream(const void* queries, const void* docs, int64_t Q, int
                            int32_t* out_n, irc_stream_t stream);
 int irc_rerank_stream_tile(void);
 
+/* irc_rerank_topk on an e4m3 shard (the fp8 corpus, BASELINE config C5): queries [Q, D]
+ * and docs [N, D] are e4m3fn bytes as irc_quantize_fp8 writes them.  The raw score is the
+ * fp32 sum over D of the products of the decoded values (each product exact in fp32), in
+ * one fixed order per (query, doc); the reported score is raw * score_scale, score_scale a
+ * power of two as irc_scan_topk_fp8 requires it (else IRC_E_INVALID), so the product is
+ * exact.  Everything else -- candidate lists, foreign ids, ranking rule, padding, limits,
+ * validation order, workspace (irc_rerank_topk_workspace) -- is irc_rerank_topk's; D as
+ * irc_scan_topk_fp8 accepts.  A NaN code ranks in no defined place. */
+int irc_rerank_topk_fp8(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,
+                        const int32_t* cand, const int64_t* cand_off, int64_t n_cand,
+                        int64_t k, int64_t doc_offset, float score_scale, void* workspace,
+                        int64_t workspace_bytes, float* out_score, int64_t* out_idx,
+                        int32_t* out_n, irc_stream_t stream);
+
+/* irc_rerank_topk_stream on an e4m3 shard: the shard streams through the unit-scale e4m3
+ * MFMA loop (128-byte K-tiles, so D % 128 == 0: D = 64 is IRC_E_INVALID here) and the
+ * candidates' scores, times score_scale, are picked out of the score tiles.  Lists
+ * ASCENDING as for irc_rerank_topk_stream; arguments and score_scale as
+ * irc_rerank_topk_fp8.  The summation order is the MFMA loop's, fixed per (query, doc)
+ * whatever the tile; on values whose sums are exact the two e4m3 entries agree bitwise. */
+int irc_rerank_topk_stream_fp8(const void* queries, const void* docs, int64_t Q, int64_t N,
+                               int64_t D, const int32_t* cand, const int64_t* cand_off,
+                               int64_t n_cand, int64_t k, int64_t doc_offset,
+                               float score_scale, void* workspace, int64_t workspace_bytes,
+                               float* out_score, int64_t* out_idx, int32_t* out_n,
+                               irc_stream_t stream);
+
 /* Raw score tile for tests / diagnostics: out[Q, N] fp32 = queries . docs^T
  * using the same MFMA path as irc_scan_topk. */
 int irc_scan_scores(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,

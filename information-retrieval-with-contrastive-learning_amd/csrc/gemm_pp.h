@@ -90,6 +90,9 @@ struct PArgs {
   const int64_t* cand_off;
   int64_t n_cand;
   int64_t doc_offset;
+  // e4m3 pick (run_pick with fp8): the key's score is C[q][doc] * score_scale, a power of
+  // two (exact); the bf16 pick does not read it
+  float score_scale;
 };
 
 int splits_for(int out_f32, int epi, int64_t M, int64_t N, int64_t K, int64_t batch,
@@ -107,7 +110,9 @@ void run(int out_f32, int la, int lb, int epi, const PArgs& a, int64_t batch, in
 void run_scan(const PArgs& a, hipStream_t st, bool fp8 = false);
 // candidate pick: A = queries [M=Q][K=D], B = docs [N][D], bf16, EPI_PICK (see PArgs);
 // M, N > 0 and ceil(M / 256) * ceil(N / 256) < 2^31
-void run_pick(const PArgs& a, hipStream_t st);
+// fp8: e4m3 operands, K / lda / ldb in 2-byte units (D/2, D % 128 == 0), keys scaled by
+// a.score_scale
+void run_pick(const PArgs& a, hipStream_t st, bool fp8 = false);
 // doc-tile width of run_pick
 constexpr int PICK_TILE = 256;
 // raw fp32 C = A . B^T of e4m3 operands (K, lda, ldb in 2-byte units; vec_c layout)

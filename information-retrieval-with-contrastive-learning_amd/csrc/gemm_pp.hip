@@ -804,8 +804,11 @@ __device__ __forceinline__ void epilogue_scan_lists(const PArgs& g, const f32x4 
 // rerank_select_kernel (rerank.hip) ranks.  The lists are ascending in global id, so the
 // candidates of query q that fall into this doc tile are one contiguous range [lo, hi) of
 // its list: two lower bounds per query, taken BEFORE the main loop and kept in the 8 KB
-// of LDS past the two K-major K-tile buffers (which the bf16 main loop never touches).  A
-// tile no query of which has a candidate in it returns there, without the main loop.
+// of LDS past the two K-major K-tile buffers (which the bf16 and the unit-scale e4m3 main
+// loops never touch: both stage and read lds + {0, 1} * buf_bytes(true, true) only; the MX
+// loop keeps its block scales there).  A tile no query of which has a candidate in it
+// returns there, without the main loop.  F8 == 1 (e4m3 shards): the key's score is the
+// accumulator times g.score_scale.
 constexpr int PICK_OFF = 2 * buf_bytes(true, true);  // 128 KB
 static_assert(PICK_OFF + 2 * BM * 8 + 16 <= LDS_BYTES, "pick ranges past the K-tile buffers");
 
@@ -860,6 +863,7 @@ __device__ __forceinline__ bool pick_ranges(const PArgs& g, char* lds, int m0, i
 // is read from the staged row at its column and its key goes to keys[j].  Nothing
 // depends on scheduling (no atomics: j is the candidate's own place).  A column outside
 // the tile (a list that broke the ascending contract) is skipped before any access.
+template <int F8 = 0>
 __device__ __forceinline__ void epilogue_pick(const PArgs& g, const f32x4 (&acc)[8][4], char* lds,
                                               int m0, int n0, int grp, int wn, int lane) {
   float* S = reinterpret_cast<float*>(lds);
@@ -897,8 +901,12 @@ __device__ __forceinline__ void epilogue_pick(const PArgs& g, const f32x4 (&acc)
       for (int u = 0; u < 4; ++u) {
         const int64_t j = j0 + 8 * u;
         const int64_t col = (int64_t)id[u] - first;
-        if (j < hi && col >= 0 && col < nval)
-          g.keys[j] = make_key(row[(int)col ^ flip], (uint32_t)id[u]);
+        if (j < hi && col >= 0 && col < nval) {
+          if constexpr (F8 != 0)
+            g.keys[j] = make_key(row[(int)col ^ flip] * g.score_scale, (uint32_t)id[u]);
+          else
+            g.keys[j] = make_key(row[(int)col ^ flip], (uint32_t)id[u]);
+        }
       }
     }
     lds_barrier();  // every reader is done with S before the next pass writes it
@@ -951,7 +959,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
 
   if (EPI == EPI_SCAN) PSTAMP(0);
   if constexpr (EPI == EPI_PICK) {
-    static_assert(AK && BK_ && F8 == 0, "the pick ranges live past two K-major buffers");
+    static_assert(AK && BK_ && F8 != 2, "the pick ranges live past two K-major buffers");
     if (!pick_ranges(g, lds, m0, n0)) return;  // no candidate in this tile
   }
   f32x4 acc[8][4];
@@ -970,7 +978,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
     return;
   }
   if constexpr (EPI == EPI_PICK) {
-    epilogue_pick(g, acc, lds, m0, n0, grp, wn, lane);
+    epilogue_pick<F8>(g, acc, lds, m0, n0, grp, wn, lane);
     return;
   }
 #ifdef IRC_PP_DIAG_NOEPI  // diagnostic build: main loop only (a guarded store of the sum of
@@ -1237,10 +1245,14 @@ void run_scan(const PArgs& a, hipStream_t st, bool fp8) {
                        dim3(NT), 0, st, a);
 }
 
-void run_pick(const PArgs& a, hipStream_t st) {
+void run_pick(const PArgs& a, hipStream_t st, bool fp8) {
   const int64_t tiles = ((int64_t)(a.M + 255) / 256) * ((a.N + 255) / 256);
-  hipLaunchKernelGGL((gemm_pp_kernel<true, true, float, EPI_PICK>), dim3((unsigned)tiles),
-                     dim3(NT), 0, st, a);
+  if (fp8)
+    hipLaunchKernelGGL((gemm_pp_kernel<true, true, float, EPI_PICK, 1>), dim3((unsigned)tiles),
+                       dim3(NT), 0, st, a);
+  else
+    hipLaunchKernelGGL((gemm_pp_kernel<true, true, float, EPI_PICK>), dim3((unsigned)tiles),
+                       dim3(NT), 0, st, a);
 }
 
 void run_scores_fp8(const PArgs& a, hipStream_t st) {

@@ -32,7 +32,13 @@
 //    query's candidates are picked out of the score tile (gemm_pp.hip, EPI_PICK; lists
 //    ascending in global id).  rerank_foreign_kernel zeroes the keys of the ids outside
 //    the shard, a prefix and a suffix of every list; the select is the same kernel.
+//  * irc_rerank_topk_fp8 / irc_rerank_topk_stream_fp8 do both on e4m3 shards (rows of D
+//    bytes): rerank_score_fp8_kernel decodes with v_cvt_pk_f32_fp8, the stream runs the
+//    unit-scale e4m3 MFMA loop (gemm_pp.hip, F8 = 1).  Scores are the fp32 sums of the exact
+//    products times a power-of-two score_scale; keys, foreign ids and select as above.
 #include <stdint.h>
+
+#include <cmath>
 
 #include "gemm_pp.h"
 #include "irc_common.h"
@@ -150,6 +156,107 @@ __global__ __launch_bounds__(RR_CHUNK) void rerank_score_kernel(
     if (sub == r) myscore = acc;
   }
   if (i < n_cand) keys[i] = myrow >= 0 ? make_key(myscore, gid) : 0ull;
+}
+
+// acc += <a, b> over the 4 e4m3 pairs of one 32-bit word, element order 0..3
+// (v_cvt_pk_f32_fp8 on each word half; an e4m3 product is exact in fp32)
+__device__ __forceinline__ float dot4_e4m3(uint32_t a, uint32_t b, float acc) {
+  const auto a0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a, false);
+  const auto b0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)b, false);
+  const auto a1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a, true);
+  const auto b1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)b, true);
+  acc = fmaf(a0[0], b0[0], acc);
+  acc = fmaf(a0[1], b0[1], acc);
+  acc = fmaf(a1[0], b1[0], acc);
+  acc = fmaf(a1[1], b1[1], acc);
+  return acc;
+}
+
+// rerank_score_kernel for e4m3 shards (irc_rerank_topk_fp8): rows of D bytes.  The same
+// walk, owner searches and 8-lane row sharing; lane s reads the 16-byte pieces s, s + 8,
+// ... (one 128-byte granule per step), and at D = 64, where a row is half a granule, the
+// 8-byte pieces s.  The query slice stays in registers as codes.  One summation order per
+// (query, doc): each lane's pieces ascending in one fmaf chain, then xor-shuffles 1, 2, 4.
+// The key's score is the sum times score_scale (a power of two: exact).
+template <int D>
+__global__ __launch_bounds__(RR_CHUNK) void rerank_score_fp8_kernel(
+    const unsigned char* __restrict__ queries, const unsigned char* __restrict__ docs, int Q,
+    int64_t N, const int32_t* __restrict__ cand, const int64_t* __restrict__ cand_off,
+    int64_t n_cand, int64_t doc_offset, float score_scale, uint64_t* __restrict__ keys) {
+  constexpr int PW = D >= 128 ? 4 : 2;          // 32-bit words per piece
+  constexpr int NC = D / (RR_LPR * PW * 4);     // pieces per lane per row
+  static_assert(NC * RR_LPR * PW * 4 == D, "a row is a whole number of 8-lane steps");
+  typedef uint32_t piece_t __attribute__((ext_vector_type(PW)));
+  const int tid = threadIdx.x;
+  const int sub = tid & (RR_LPR - 1);
+  const int64_t i0 = (int64_t)blockIdx.x * RR_CHUNK;
+  const int64_t i = i0 + tid;
+  const int64_t ilast = (i0 + RR_CHUNK <= n_cand ? i0 + RR_CHUNK : n_cand) - 1;
+
+  // the chunk's first and last owner, then this thread's own (rerank_score_kernel)
+  int qa, qb;
+  {
+    int lo_a = 0, hi_a = Q, lo_b = 0, hi_b = Q;
+    while (lo_a < hi_a || lo_b < hi_b) {
+      if (lo_a < hi_a) {
+        const int mid = (lo_a + hi_a) >> 1;
+        if (cand_off[mid + 1] <= i0) lo_a = mid + 1;
+        else hi_a = mid;
+      }
+      if (lo_b < hi_b) {
+        const int mid = (lo_b + hi_b) >> 1;
+        if (cand_off[mid + 1] <= ilast) lo_b = mid + 1;
+        else hi_b = mid;
+      }
+    }
+    qa = lo_a;
+    qb = lo_b;
+  }
+  int myq = 0;
+  int myrow = -1;  // row in this shard, -1: not scored (past the end / another shard)
+  uint32_t gid = 0;
+  if (i < n_cand) {
+    myq = owner_of(cand_off, qa, qb, i);
+    myq = myq < Q - 1 ? myq : Q - 1;  // cand_off[Q] < n_cand (caller's error): stay in bounds
+    const int64_t id = (int64_t)cand[i];
+    const int64_t r = id - doc_offset;
+    if (r >= 0 && r < N) {
+      myrow = (int)r;
+      gid = (uint32_t)id;
+    }
+  }
+
+  piece_t qv[NC];
+  int qcur = -1;
+  float myscore = 0.f;
+#pragma unroll 1
+  for (int r = 0; r < RR_LPR; ++r) {
+    const int row = __shfl(myrow, r, RR_LPR);
+    const int qq = __shfl(myq, r, RR_LPR);
+    float acc = 0.f;
+    if (row >= 0) {  // uniform over the 8-lane group
+      if (qq != qcur) {
+        const piece_t* qp = reinterpret_cast<const piece_t*>(queries + (int64_t)qq * D) + sub;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) qv[c] = qp[c * RR_LPR];
+        qcur = qq;
+      }
+      const piece_t* dp = reinterpret_cast<const piece_t*>(docs + (int64_t)row * D) + sub;
+      piece_t dv[NC];
+#pragma unroll
+      for (int c = 0; c < NC; ++c) dv[c] = dp[c * RR_LPR];
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+#pragma unroll
+        for (int w = 0; w < PW; ++w) acc = dot4_e4m3(qv[c][w], dv[c][w], acc);
+    }
+    // every lane takes part (the exchange stays inside the 8-lane group)
+    acc += __shfl_xor(acc, 1, 64);
+    acc += __shfl_xor(acc, 2, 64);
+    acc += __shfl_xor(acc, 4, 64);
+    if (sub == r) myscore = acc;
+  }
+  if (i < n_cand) keys[i] = myrow >= 0 ? make_key(myscore * score_scale, gid) : 0ull;
 }
 
 __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
@@ -441,6 +548,11 @@ static bool supported_d(int64_t D) {  // the scan's set (scan_topk.hip)
   return D == 64 || D == 128 || D == 256 || D == 384 || D == 512 || D == 768 || D == 1024;
 }
 
+static bool pow2_scale(float s) {  // irc_scan_topk_fp8's rule (scan_topk.hip)
+  int e;
+  return s > 0.f && std::isfinite(s) && std::frexp(s, &e) == 0.5f;
+}
+
 static size_t workspace_bytes_for(int64_t n_cand) {
   const size_t keys = (size_t)(n_cand > 0 ? n_cand : 0) * 8;
   return ((keys + 255) & ~(size_t)255) + 256;
@@ -580,4 +692,114 @@ extern "C" int irc_rerank_topk_stream(const void* queries, const void* docs, int
     if (int rc = check_launch("rerank_stream_score")) return rc;
   }
   return launch_select(keys, cand_off, Q, n_cand, k, out_score, out_idx, out_n, st);
+}
+
+// The two e4m3 entries: irc_rerank_topk's checks in its order, the e4m3 ones after the D
+// check, then one of the two scoring passes and the shared select.
+static int rerank_fp8_impl(bool stream, const void* queries, const void* docs, int64_t Q,
+                           int64_t N, int64_t D, const int32_t* cand, const int64_t* cand_off,
+                           int64_t n_cand, int64_t k, int64_t doc_offset, float score_scale,
+                           void* workspace, int64_t workspace_bytes, float* out_score,
+                           int64_t* out_idx, int32_t* out_n, irc_stream_t stream_) {
+  IRC_REQUIRE(Q >= 0 && N >= 0 && n_cand >= 0, "rerank_topk_fp8: negative size");
+  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "rerank_topk_fp8: k=%lld outside [1, %d]", (long long)k,
+              RR_MAXK);
+  IRC_REQUIRE(supported_d(D), "rerank_topk_fp8: unsupported D=%lld", (long long)D);
+  IRC_REQUIRE(!stream || D % 128 == 0,
+              "rerank_topk_fp8: unsupported D=%lld for the stream method (D %% 128 == 0)",
+              (long long)D);
+  IRC_REQUIRE(pow2_scale(score_scale), "rerank_topk_fp8: score_scale must be a power of two");
+  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
+              "rerank_topk_fp8: global doc ids must fit int32 (doc_offset + N < 2^31)");
+  IRC_REQUIRE(Q < (1ll << 31) - 1, "rerank_topk_fp8: Q too large");
+  IRC_REQUIRE(n_cand < (1ll << 31) * RR_CHUNK, "rerank_topk_fp8: n_cand too large");
+  IRC_REQUIRE(!stream || ((Q + 255) / 256) * ((N + 255) / 256) < (1ll << 31),
+              "rerank_topk_fp8: Q x N too large for the stream method");
+  if (workspace == nullptr || workspace_bytes < (int64_t)workspace_bytes_for(n_cand)) {
+    set_error("rerank_topk_fp8: workspace %lld < required %lld bytes", (long long)workspace_bytes,
+              (long long)workspace_bytes_for(n_cand));
+    return IRC_E_WORKSPACE;
+  }
+  if (Q == 0) return IRC_OK;
+  IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n,
+              "rerank_topk_fp8: null pointer");
+  IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)),
+              "rerank_topk_fp8: null candidates / docs");
+  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
+              "rerank_topk_fp8: queries and docs must be 16-byte aligned");
+  hipStream_t st = as_stream(stream_);
+  uint64_t* keys = static_cast<uint64_t*>(workspace);
+  if (n_cand > 0 && !stream) {
+    const unsigned blocks = (unsigned)((n_cand + RR_CHUNK - 1) / RR_CHUNK);
+    const unsigned char* qp = static_cast<const unsigned char*>(queries);
+    const unsigned char* dp = static_cast<const unsigned char*>(docs);
+    prof_begin(st);
+#define IRC_RR_CASE(DD)                                                                       \
+  case DD:                                                                                    \
+    hipLaunchKernelGGL((rerank_score_fp8_kernel<DD>), dim3(blocks), dim3(RR_CHUNK), 0, st, qp, \
+                       dp, (int)Q, N, cand, cand_off, n_cand, doc_offset, score_scale, keys); \
+    break;
+    switch (D) {
+      IRC_RR_CASE(64)
+      IRC_RR_CASE(128)
+      IRC_RR_CASE(256)
+      IRC_RR_CASE(384)
+      IRC_RR_CASE(512)
+      IRC_RR_CASE(768)
+      default: IRC_RR_CASE(1024)
+    }
+#undef IRC_RR_CASE
+    prof_end("rerank_fp8_score", st, (double)n_cand * D);  // the gathered row bytes
+    if (int rc = check_launch("rerank_score_fp8_kernel")) return rc;
+  }
+  if (n_cand > 0 && stream) {
+    prof_begin(st);
+    hipLaunchKernelGGL(rerank_foreign_kernel, dim3((unsigned)Q, RF_Y), dim3(RF_NT), 0, st, cand,
+                       cand_off, n_cand, doc_offset, N, keys);
+    if (N > 0) {
+      gpp::PArgs a{};
+      a.A = static_cast<const unsigned short*>(queries);
+      a.B = static_cast<const unsigned short*>(docs);
+      a.M = (int)Q;
+      a.N = (int)N;
+      a.K = (int)(D / 2);  // 2-byte units
+      a.kchunk = a.K;
+      a.lda = a.K;
+      a.ldb = a.K;
+      a.keys = keys;
+      a.cand = cand;
+      a.cand_off = cand_off;
+      a.n_cand = n_cand;
+      a.doc_offset = doc_offset;
+      a.score_scale = score_scale;
+      gpp::run_pick(a, st, true);
+    }
+    // the bytes the pass streams: the shard once per query tile
+    prof_end("rerank_fp8_stream_score", st, (double)((Q + 255) / 256) * (double)N * D);
+    if (int rc = check_launch("rerank_fp8_stream_score")) return rc;
+  }
+  return launch_select(keys, cand_off, Q, n_cand, k, out_score, out_idx, out_n, st);
+}
+
+extern "C" int irc_rerank_topk_fp8(const void* queries, const void* docs, int64_t Q, int64_t N,
+                                   int64_t D, const int32_t* cand, const int64_t* cand_off,
+                                   int64_t n_cand, int64_t k, int64_t doc_offset,
+                                   float score_scale, void* workspace, int64_t workspace_bytes,
+                                   float* out_score, int64_t* out_idx, int32_t* out_n,
+                                   irc_stream_t stream) {
+  return rerank_fp8_impl(false, queries, docs, Q, N, D, cand, cand_off, n_cand, k, doc_offset,
+                         score_scale, workspace, workspace_bytes, out_score, out_idx, out_n,
+                         stream);
+}
+
+extern "C" int irc_rerank_topk_stream_fp8(const void* queries, const void* docs, int64_t Q,
+                                          int64_t N, int64_t D, const int32_t* cand,
+                                          const int64_t* cand_off, int64_t n_cand, int64_t k,
+                                          int64_t doc_offset, float score_scale, void* workspace,
+                                          int64_t workspace_bytes, float* out_score,
+                                          int64_t* out_idx, int32_t* out_n,
+                                          irc_stream_t stream) {
+  return rerank_fp8_impl(true, queries, docs, Q, N, D, cand, cand_off, n_cand, k, doc_offset,
+                         score_scale, workspace, workspace_bytes, out_score, out_idx, out_n,
+                         stream);
 }

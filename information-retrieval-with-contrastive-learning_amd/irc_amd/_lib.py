@@ -44,6 +44,10 @@ SIGNATURES = {
     "irc_rerank_topk_stream": (I32, [P, P, I64, I64, I64, P, P, I64, I64, I64, P, I64, P, P, P,
                                      P]),
     "irc_rerank_stream_tile": (I32, []),
+    "irc_rerank_topk_fp8": (I32, [P, P, I64, I64, I64, P, P, I64, I64, I64, F32, P, I64, P, P, P,
+                                  P]),
+    "irc_rerank_topk_stream_fp8": (I32, [P, P, I64, I64, I64, P, P, I64, I64, I64, F32, P, I64, P,
+                                         P, P, P]),
     "irc_scan_topk_fp8_workspace": (I64, [I64, I64, I64, I64]),
     "irc_scan_topk_fp8": (I32, [P, P, I64, I64, I64, I64, I64, F32, P, I64, P, P, P]),
     "irc_scan_scores_fp8": (I32, [P, P, I64, I64, I64, P, P]),

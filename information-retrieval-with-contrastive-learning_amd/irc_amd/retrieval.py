@@ -104,11 +104,15 @@ def quantize_fp8(x: torch.Tensor, scale: float = FP8_SCALE) -> torch.Tensor:
     return out
 
 
-def _fp8_operands(queries, docs):
-    require_hip(queries, docs)
-    for t in (queries, docs):
+def _require_e4m3(*tensors):
+    for t in tensors:
         if t.dtype != torch.uint8:
             raise TypeError("fp8 scan operands are e4m3 bytes (torch.uint8, see quantize_fp8)")
+
+
+def _fp8_operands(queries, docs):
+    require_hip(queries, docs)
+    _require_e4m3(queries, docs)
     q, d = queries.contiguous(), docs.contiguous()
     if d.shape[1] != q.shape[1]:
         raise ValueError(f"dim mismatch: queries D={q.shape[1]}, docs D={d.shape[1]}")
@@ -193,9 +197,13 @@ RERANK_METHODS = ("gather", "stream")
 _STREAM_CROSSOVER = ((1, None), (16, 0.15634670821855476), (64, 0.03685017313384864),
                      (256, 0.010609454861342326))
 _STREAM_MIN_TILES = 4  # below this many doc tiles the shard is too small to matter
+# The same for e4m3 shards (rerank_topk_fp8): the ``crossover_frac_stream`` of
+# profiles/rerank_fp8_probe.json (tools/rerank_probe.py --dtype fp8; the same shard as e4m3).
+_STREAM_CROSSOVER_FP8 = ((1, None), (16, 0.24292551185132844), (64, 0.05971435860633441),
+                         (256, 0.015683947640214146))
 
 
-def rerank_method(Q: int, N: int, D: int, n_cand: int) -> str:
+def rerank_method(Q: int, N: int, D: int, n_cand: int, dtype: str = "bf16") -> str:
     """"gather" or "stream": the faster scoring method of ``rerank_topk`` for Q queries
     with n_cand candidates in all against a shard of N docs (pure host arithmetic, no
     device access).  "stream" once the mean list length n_cand / Q reaches the measured
@@ -204,12 +212,20 @@ def rerank_method(Q: int, N: int, D: int, n_cand: int) -> str:
     16, 64, 256 and held constant beyond them; where gather won every measured cell of a
     Q (Q = 1), and between such a Q and the next measured one, the answer is "gather".  A shard below 4 doc tiles (RERANK_STREAM_TILE docs each) is
     always gathered.  The crossovers were measured at D = 768; both methods' scoring cost
-    is proportional to D, so D does not enter.  Monotone in n_cand."""
+    is proportional to D, so D does not enter.  Monotone in n_cand.
+
+    ``dtype="fp8"``: the choice for ``rerank_topk_fp8``, by the same rule on its own
+    table (profiles/rerank_fp8_probe.json); "gather" wherever the e4m3 stream kernel does
+    not run (D % 128 != 0)."""
     import math
 
+    if dtype not in ("bf16", "fp8"):
+        raise ValueError(f"dtype must be 'bf16' or 'fp8', not {dtype!r}")
     if Q <= 0 or n_cand <= 0 or N < _STREAM_MIN_TILES * 256:
         return "gather"
-    pts = _STREAM_CROSSOVER
+    if dtype == "fp8" and D % 128 != 0:
+        return "gather"
+    pts = _STREAM_CROSSOVER_FP8 if dtype == "fp8" else _STREAM_CROSSOVER
     if Q <= pts[0][0]:
         frac = pts[0][1]
     elif Q >= pts[-1][0]:
@@ -273,10 +289,18 @@ def rerank_topk(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
     require_hip(queries, docs, cand, cand_off)
     q = contig(queries, torch.bfloat16)
     d = contig(docs, torch.bfloat16)
+    if d.shape[1] != q.shape[1]:
+        raise ValueError(f"dim mismatch: queries D={q.shape[1]}, docs D={d.shape[1]}")
+    entry = "irc_rerank_topk_stream" if method == "stream" else "irc_rerank_topk"
+    return _rerank_call(entry, (), q, d, cand, cand_off, k, doc_offset, ws_tag, method, ascending)
+
+
+def _rerank_call(entry, extra, q, d, cand, cand_off, k, doc_offset, ws_tag, method, ascending):
+    """The part of ``rerank_topk`` and ``rerank_topk_fp8`` after their operand checks: the
+    id handling, the sort under "stream", the outputs and the native call (``extra``: the
+    entry's arguments between doc_offset and the workspace)."""
     Q, D = q.shape
     N = d.shape[0]
-    if d.shape[1] != D:
-        raise ValueError(f"dim mismatch: queries D={D}, docs D={d.shape[1]}")
     if cand.dtype not in (torch.int32, torch.int64):
         raise TypeError(f"cand must be int32 or int64, not {cand.dtype}")
     if cand_off.numel() != Q + 1:
@@ -297,11 +321,30 @@ def rerank_topk(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
     out_n = torch.empty((Q,), dtype=torch.int32, device=q.device)
     nbytes = int(_lib.fn("irc_rerank_topk_workspace")(Q, n_cand, k))
     ws = workspace(nbytes, q.device, ws_tag)
-    entry = "irc_rerank_topk_stream" if method == "stream" else "irc_rerank_topk"
     _lib.call(entry, ptr(q), ptr(d), Q, N, D, ptr(c), ptr(off), n_cand, k,
-              doc_offset, ptr(ws), ws.numel(), ptr(out_s), ptr(out_i), ptr(out_n),
+              doc_offset, *extra, ptr(ws), ws.numel(), ptr(out_s), ptr(out_i), ptr(out_n),
               stream_ptr(q.device))
     return out_s, out_i, out_n
+
+
+def rerank_topk_fp8(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
+                    cand_off: torch.Tensor, k: int, doc_offset: int = 0,
+                    score_scale: float = 1.0, ws_tag: str = "rerank", method: str = "gather",
+                    ascending: bool = False):
+    """``rerank_topk`` over e4m3 operands: queries [Q, D] and docs [N, D] are uint8 codes
+    (``quantize_fp8``).  The scores are the fp32 dot products of the decoded values times
+    ``score_scale`` (a power of two), as ``scan_topk_fp8`` reports them; candidates, ids,
+    ``method``, ``ascending`` and the outputs are ``rerank_topk``'s.  "gather" is
+    irc_rerank_topk_fp8, "stream" irc_rerank_topk_stream_fp8 (D % 128 == 0); on values
+    whose sums are exact in fp32 the two agree bitwise."""
+    if method not in RERANK_METHODS:
+        raise ValueError(f"method must be one of {RERANK_METHODS}, not {method!r}")
+    _require_e4m3(queries, docs)  # a wrong dtype is a TypeError on any device
+    q, d = _fp8_operands(queries, docs)
+    require_hip(cand, cand_off)
+    entry = "irc_rerank_topk_stream_fp8" if method == "stream" else "irc_rerank_topk_fp8"
+    return _rerank_call(entry, (float(score_scale),), q, d, cand, cand_off, k, doc_offset, ws_tag,
+                        method, ascending)
 
 
 def expand_ranges(cand: torch.Tensor, cand_off: torch.Tensor, row_off: torch.Tensor):
@@ -435,7 +478,10 @@ class ShardedDenseIndex:
                           method: str = "gather", ascending: bool = False):
         """Top-k of each query over its own candidate docs only (global ids, the CSR pair
         ``SparseIndex.candidates`` / ``expand_ranges`` leave on the device): (scores
-        [Q, k], idx [Q, k], n [Q]) as ``rerank_topk``.  bf16 shards, single process.
+        [Q, k], idx [Q, k], n [Q]) as ``rerank_topk``.  Single process; bf16 and fp8 shards
+        (on an fp8 index the queries are quantised with ``fp8_scale`` and ``rerank_topk_fp8``
+        ranks the e4m3 codes, scores descaled exactly as ``search`` descales them; the
+        measured fp8 tables are in DESIGN.md 6e).
 
         ``method``: "gather" (the default), "stream", or "auto", which takes
         ``rerank_method``'s choice when ``ascending=True`` and "gather" otherwise;
@@ -474,8 +520,11 @@ class ShardedDenseIndex:
         5.8 % at Q = 16, and above 25 % at Q = 1.  The scoring pass gathers 4.8-7.6 TB/s of
         row bytes from 160k candidates up (lists of one call that overlap hit the caches)
         and is latency-bound below."""
-        if self.dtype == "fp8":
-            raise ValueError("search_candidates scores bf16 shards only (dtype='fp8' index)")
+        if self.dtype == "fp8" and self.docs.dtype != torch.uint8:
+            # before anything touches the queries or the device: a hand-built index or a
+            # damaged header on load()
+            raise ValueError("fp8 index: the shard is not e4m3 bytes (torch.uint8) but "
+                             f"{self.docs.dtype}")
         if self._sharded():
             raise NotImplementedError(
                 "search_candidates over a process group: the all_gather of the queries and "
@@ -484,7 +533,13 @@ class ShardedDenseIndex:
         if method == "auto":
             # the stream method's sort of unsorted lists is not in the measured crossovers
             method = "gather" if not ascending else rerank_method(
-                queries.shape[0], self.docs.shape[0], self.docs.shape[1], cand.numel())
+                queries.shape[0], self.docs.shape[0], self.docs.shape[1], cand.numel(),
+                dtype=self.dtype)
+        if self.dtype == "fp8":
+            q8 = quantize_fp8(queries, self.fp8_scale)
+            return rerank_topk_fp8(q8, self.docs, cand, cand_off, k, self.doc_offset,
+                                   1.0 / (self.fp8_scale * self.fp8_scale), ws_tag=ws_tag,
+                                   method=method, ascending=ascending)
         return rerank_topk(queries, self.docs, cand, cand_off, k, self.doc_offset, ws_tag=ws_tag,
                            method=method, ascending=ascending)
 

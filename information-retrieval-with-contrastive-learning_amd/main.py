@@ -3,7 +3,7 @@
     python main.py [--config config.yaml] [--data doc|fever] [--gpu 0] [--ckpt X]
                    [--model LSTM|BERT] [--loss InfoNCE] [--opt adam] [--sample uniform|tf_idf]
                    [--seed 1337] [--logdir log] [--ckptdir ckpt] [--retrieval sparse|dense|hybrid]
-                   [--rerank-method auto|gather|stream]
+                   [--rerank-method auto|gather|stream] [--index-dtype bf16|fp8]
 
 Multi-GPU (one process per GPU):
     torchrun --nproc-per-node N --master-addr 127.0.0.1 main.py [same flags]
@@ -68,6 +68,11 @@ def get_args(argv=None):
                         "crossovers. Same ranking contract either way: the exact top-k over "
                         "the candidates only; scores may differ in the last bits (another "
                         "fp32 summation order)")
+    p.add_argument("--index-dtype", default="bf16", type=str, choices=["bf16", "fp8"],
+                   help="--retrieval dense / hybrid: how the evidence corpus is kept in HBM. "
+                        "bf16 (default), or fp8: e4m3 bytes at half the size, the claims "
+                        "quantised with the same scale per search and the scores those of "
+                        "the quantised embeddings")
     return p.parse_args(argv)
 
 

@@ -126,7 +126,7 @@ def predict_dense(args, k=100):
                 texts.append(line)
     lo, hi = shard_bounds(len(texts), world, rank)
     index = ShardedDenseIndex(encode_corpus(model, texts[lo:hi], args.device), doc_offset=lo,
-                              group=group)
+                              group=group, dtype=getattr(args, "index_dtype", "bf16"))
     dim = model.loss_config["dim"]
     hits = total = 0
     for batch in tqdm(loader, desc="Iteration", disable=rank != 0):
@@ -192,7 +192,8 @@ def predict_hybrid(args, k=100):
     the bi-encoder's exact top-k over the filter's candidates only.  Prints each batch's
     latency and the evidence recall@k (a claim with no candidates is a miss); returns
     recall@k.  Single process.  ``args.rerank_method`` (default "auto") picks the scoring
-    method per batch; the ranking contract is the same either way."""
+    method per batch; the ranking contract is the same either way.  ``args.index_dtype``
+    (default "bf16"): "fp8" keeps the corpus as e4m3 bytes and ranks the quantised embeddings."""
     assert args.ckpt is not None
     if getattr(args, "dist_group", None) is not None and int(getattr(args, "world_size", 1)) > 1:
         raise NotImplementedError("--retrieval hybrid runs in a single process: the collective "
@@ -208,7 +209,8 @@ def predict_hybrid(args, k=100):
     sparse_index = SparseIndex(count_matrix, ngram=metadata["ngram"], device=args.device)
     titles, texts, row_off = hybrid_corpus(loader.dataset.wiki, metadata["doc_dict"][1])
     row_off = torch.tensor(row_off, dtype=torch.int64, device=args.device)
-    index = ShardedDenseIndex(encode_corpus(model, texts, args.device))
+    index = ShardedDenseIndex(encode_corpus(model, texts, args.device),
+                              dtype=getattr(args, "index_dtype", "bf16"))  # main.py --index-dtype
     method = getattr(args, "rerank_method", "auto")  # main.py --rerank-method
     hits = total = 0
     for batch in tqdm(loader, desc="Iteration"):

@@ -4,6 +4,8 @@ cross.
     python tools/rerank_probe.py [--n 250000] [--d 768] [--k 100] [--rounds 10] [--sets 4]
     python tools/rerank_probe.py --tables profiles/rerank_probe.json   # the documents' tables
     python tools/rerank_probe.py --tables profiles/rerank_stream_probe.json  # + stream table
+    python tools/rerank_probe.py --dtype fp8 > profiles/rerank_fp8_probe.json  # e4m3 shard
+    python tools/rerank_probe.py --tables profiles/rerank_fp8_probe.json  # + fp8 / bf16 table
 
 One MI355X, the C3 shard (250k x 768 bf16, larger than the Infinity Cache), random
 ascending candidate lists of 0.1 / 1 / 5 / 25 % of the shard per query, Q in {1, 16, 64,
@@ -18,6 +20,12 @@ The streamed method (rerank_topk(method="stream", ascending=True)) is a third pa
 same alternation -- same windows, same list draws -- with its own profiled pass
 (rerank_stream_score, rerank_select) and a gather-against-stream crossover per Q
 (``crossover_frac_stream``, the constants of retrieval.rerank_method).
+``--dtype fp8``: the same cells on the same shard quantised to e4m3 (quantize_fp8, scale
+16): rerank_topk_fp8 gathered and streamed and scan_topk_fp8 take the three places above,
+and the bf16 gathered and streamed calls of the same cells and list draws join the
+alternation window by window (``bf16_rerank_call_us``, ``bf16_stream_call_us``), so every
+fp8 time stands beside the bf16 time of the same run.  The crossovers of that file are the
+constants of retrieval.rerank_method(dtype="fp8").
 Prints a table to stderr and ONE JSON line to stdout."""
 import argparse
 import ctypes
@@ -93,6 +101,21 @@ def stream_tables(r):
         print(f"    {n:>8,} ({100 * frac:g} %)".ljust(26) + "".join(
             f"{row[q]['rerank_call_us']:>9,.0f} / {row[q]['stream_call_us']:<6,.0f}" for q in qs))
     print()
+    if r.get("dtype") == "fp8":
+        print("| Q | candidates / query | fp8 gather call | bf16 gather call | fp8 score kernel | "
+              "fp8 stream call | bf16 stream call | fp8 pick kernels | fp8 scan call |\n"
+              "|---|---|---|---|---|---|---|---|---|")
+        for c in cells:
+            print(f"| {c['Q']} | {c['cand_per_query']:,} ({100 * c['frac']:g}%) | "
+                  f"{c['rerank_call_us']:,.1f} | {c['bf16_rerank_call_us']:,.1f} | "
+                  f"{c['score_kernel_us']:,.1f} | {c['stream_call_us']:,.1f} | "
+                  f"{c['bf16_stream_call_us']:,.1f} | {c['stream_score_kernel_us']:,.1f} | "
+                  f"{c['scan_call_us']:.1f} |")
+        print()
+        slower = [(c["Q"], c["frac"], m) for c in cells for m in ("rerank", "stream")
+                  if c[f"{m}_call_us"] > c[f"bf16_{m}_call_us"]]
+        print("cells where the fp8 call is slower than its bf16 counterpart:", slower or "none")
+        print()
     print("gather-against-stream crossover:", r["crossover_frac_stream"])
     worst = max(cells, key=lambda c: c["spread_pct"]["stream"])
     print(f"largest min-max spread of the stream windows: {worst['spread_pct']['stream']:.2f}% "
@@ -150,7 +173,10 @@ def main():
                     help="independent candidate draws per cell, cycled call by call")
     ap.add_argument("--q", type=int, nargs="*", default=[1, 16, 64, 256])
     ap.add_argument("--frac", type=float, nargs="*", default=[0.001, 0.01, 0.05, 0.25])
+    ap.add_argument("--dtype", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: the e4m3 calls, with the bf16 calls of the same cells alongside")
     args = ap.parse_args()
+    fp8 = args.dtype == "fp8"
     if not torch.cuda.is_available():
         raise SystemExit("rerank_probe measures on a HIP device; none is visible")
     from irc_amd import _lib, retrieval
@@ -161,11 +187,19 @@ def main():
     docs = torch.nn.functional.normalize(
         torch.randn(args.n, args.d, generator=g)).bfloat16().to(dev)
     torch.manual_seed(2025)
+    docs8 = retrieval.quantize_fp8(docs) if fp8 else None
+    descale = 1.0 / (retrieval.FP8_SCALE * retrieval.FP8_SCALE)
+    score_span, pick_span = ((b"rerank_fp8_score", b"rerank_fp8_stream_score") if fp8 else
+                             (b"rerank_score", b"rerank_stream_score"))
     cells = []
     for Q in args.q:
         qq = torch.nn.functional.normalize(
             torch.randn(Q, args.d, generator=g)).bfloat16().to(dev)
-        scan = lambda: retrieval.scan_topk(qq, docs, args.k)  # noqa: E731
+        qq8 = retrieval.quantize_fp8(qq) if fp8 else None
+        if fp8:
+            scan = lambda: retrieval.scan_topk_fp8(qq8, docs8, args.k, 0, descale)  # noqa: E731
+        else:
+            scan = lambda: retrieval.scan_topk(qq, docs, args.k)  # noqa: E731
         for frac in args.frac:
             n = max(1, int(round(frac * args.n)))
             # a serving loop brings new lists with every batch: the calls of a window cycle
@@ -177,32 +211,46 @@ def main():
             off = torch.arange(Q + 1, device=dev, dtype=torch.int64) * n
             turn = [0]
 
-            def rer():
-                turn[0] += 1
-                return retrieval.rerank_topk(qq, docs, cands[turn[0] % args.sets], off, args.k)
+            def gathered(counter, low):
+                def call():
+                    counter[0] += 1
+                    c = cands[counter[0] % args.sets]
+                    if low:
+                        return retrieval.rerank_topk_fp8(qq8, docs8, c, off, args.k, 0, descale)
+                    return retrieval.rerank_topk(qq, docs, c, off, args.k)
+                return call
 
-            sturn = [0]
+            def streamed(counter, low):
+                def call():
+                    counter[0] += 1
+                    c = cands[counter[0] % args.sets]
+                    if low:
+                        return retrieval.rerank_topk_fp8(qq8, docs8, c, off, args.k, 0, descale,
+                                                         method="stream", ascending=True)
+                    return retrieval.rerank_topk(qq, docs, c, off, args.k, method="stream",
+                                                 ascending=True)
+                return call
 
-            def stm():
-                sturn[0] += 1
-                return retrieval.rerank_topk(qq, docs, cands[sturn[0] % args.sets], off, args.k,
-                                             method="stream", ascending=True)
-
+            rer, stm = gathered(turn, fp8), streamed([0], fp8)
+            timed = [("rerank", rer), ("stream", stm), ("scan", scan)]
+            if fp8:  # the bf16 calls of the same cell and draws, in the same alternation
+                timed += [("bf16_rerank", gathered([0], False)),
+                          ("bf16_stream", streamed([0], False))]
             est = {}
-            for name, fn in (("rerank", rer), ("stream", stm), ("scan", scan)):
+            for name, fn in timed:
                 for _ in range(3):
                     fn()
                 torch.cuda.synchronize()
                 est[name] = _window_ms(fn, 5)
             reps = {m: max(2 * args.sets, min(4000, int(args.window_ms / max(est[m], 1e-3))))
                     for m in est}
-            reps["rerank"] -= reps["rerank"] % args.sets  # every draw equally often
-            reps["stream"] -= reps["stream"] % args.sets
-            t = {"rerank": [], "stream": [], "scan": []}
-            for _ in range(args.rounds):  # alternate the three
-                t["rerank"].append(_window_ms(rer, reps["rerank"]))
-                t["stream"].append(_window_ms(stm, reps["stream"]))
-                t["scan"].append(_window_ms(scan, reps["scan"]))
+            for m in reps:
+                if m != "scan":
+                    reps[m] -= reps[m] % args.sets  # every draw equally often
+            t = {m: [] for m, _ in timed}
+            for _ in range(args.rounds):  # alternate them window by window
+                for m, fn in timed:
+                    t[m].append(_window_ms(fn, reps[m]))
             # kernel times in a pass of their own (per-launch events slow the host)
             lib.irc_prof_reset()
             lib.irc_prof_enable(1)
@@ -210,7 +258,7 @@ def main():
                 rer()
             torch.cuda.synchronize()
             lib.irc_prof_enable(0)
-            score_us, score_bytes = _prof(lib, b"rerank_score")
+            score_us, score_bytes = _prof(lib, score_span)
             select_us, _ = _prof(lib, b"rerank_select")
             lib.irc_prof_reset()
             lib.irc_prof_enable(1)
@@ -218,7 +266,7 @@ def main():
                 stm()
             torch.cuda.synchronize()
             lib.irc_prof_enable(0)
-            pick_us, _ = _prof(lib, b"rerank_stream_score")
+            pick_us, _ = _prof(lib, pick_span)
             sselect_us, _ = _prof(lib, b"rerank_select")
             stream_us = statistics.median(t["stream"]) * 1e3
             scan_us = statistics.median(t["scan"]) * 1e3
@@ -242,6 +290,10 @@ def main():
                 "spread_pct": {m: 100.0 * (max(t[m]) - min(t[m])) / statistics.median(t[m])
                                for m in t},
             }
+            for m in ("bf16_rerank", "bf16_stream"):
+                if m in t:
+                    cell[f"{m}_call_us"] = statistics.median(t[m]) * 1e3
+                    cell[f"{m}_call_us_minmax"] = [min(t[m]) * 1e3, max(t[m]) * 1e3]
             cells.append(cell)
             print(f"Q={Q:4d} frac={frac:6.3f} n_cand={Q * n:9d}  rerank {cell['rerank_call_us']:9.1f} us"
                   f"  (score {score_us:9.1f} us, {cell['score_TBps'] or 0:5.2f} TB/s; select "
@@ -255,7 +307,7 @@ def main():
         cross[str(Q)] = _crossover(row, "rerank_call_us", "scan_call_us")
         cross_stream[str(Q)] = _crossover(row, "rerank_call_us", "stream_call_us")
     print(json.dumps({"probe": "rerank_gather_stream_scan", "device": torch.cuda.get_device_name(0),
-                      "N": args.n, "D": args.d, "k": args.k, "rounds": args.rounds,
+                      "dtype": args.dtype, "N": args.n, "D": args.d, "k": args.k, "rounds": args.rounds,
                       "window_ms": args.window_ms, "sets": args.sets,
                       "gather_guide_TBps": list(GATHER_TBS), "cells": cells,
                       "crossover_frac": cross, "crossover_frac_stream": cross_stream}))
