@@ -158,6 +158,41 @@ int irc_rerank_topk_stream_fp8(const void* queries, const void* docs, int64_t Q,
                                float* out_score, int64_t* out_idx, int32_t* out_n,
                                irc_stream_t stream);
 
+/* The candidate top-k per GROUP of rows (per page, where the rows are its lines): each
+ * query's candidates collapse to the best row of every group before the select, so the
+ * outputs are the top-k distinct groups, each represented by its best row.
+ *
+ * group_off [n_groups + 1] int64, non-decreasing, in global row ids: group g owns the rows
+ * [group_off[g], group_off[g + 1]) (repeated values: empty groups).  A row below
+ * group_off[0] or from group_off[n_groups] on is in no group and is never eligible.
+ * flags: IRC_RERANK_STREAM scores as irc_rerank_topk_stream does, else as irc_rerank_topk;
+ * IRC_RERANK_E4M3 takes e4m3 operands as the two _fp8 entries do, with their score_scale
+ * (a power of two; ignored for bf16).  One entry for the four scoring forms.
+ *
+ * Every list is ASCENDING in global id and unique (irc_rerank_topk_stream's contract, here
+ * for both scoring methods), so the rows of one group are one run of consecutive
+ * candidates.  Between scoring and select, rerank_collapse_kernel zeroes every key that is
+ * not the maximum of its (query, group) run; keys carry (score, ~id), so equal scores
+ * keep the lower row id, and runs of two queries never join.  A list that breaks the
+ * contract may be ranked wrongly; nothing is read or written out of bounds.
+ *
+ * Outputs as irc_rerank_topk: out_idx the winning row of each returned group, by (score
+ * desc, id asc); out_n[q] = min(k, groups with an eligible row).  Validation in
+ * irc_rerank_topk's order (the e4m3 checks where the _fp8 entries have them), then
+ * group_off != NULL and 0 <= n_groups < 2^31 - 1.  The workspace
+ * (irc_rerank_topk_grouped_workspace) holds the key, the run maximum slot and the run
+ * head of every candidate: 24 bytes per candidate. */
+#define IRC_RERANK_STREAM 1u
+#define IRC_RERANK_E4M3 2u
+int64_t irc_rerank_topk_grouped_workspace(int64_t Q, int64_t n_cand, int64_t k);
+int irc_rerank_topk_grouped(const void* queries, const void* docs, int64_t Q, int64_t N,
+                            int64_t D, const int32_t* cand, const int64_t* cand_off,
+                            int64_t n_cand, int64_t k, int64_t doc_offset,
+                            const int64_t* group_off, int64_t n_groups, uint32_t flags,
+                            float score_scale, void* workspace, int64_t workspace_bytes,
+                            float* out_score, int64_t* out_idx, int32_t* out_n,
+                            irc_stream_t stream);
+
 /* Raw score tile for tests / diagnostics: out[Q, N] fp32 = queries . docs^T
  * using the same MFMA path as irc_scan_topk. */
 int irc_scan_scores(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,

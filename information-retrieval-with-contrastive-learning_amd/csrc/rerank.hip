@@ -36,6 +36,9 @@
 //    bytes): rerank_score_fp8_kernel decodes with v_cvt_pk_f32_fp8, the stream runs the
 //    unit-scale e4m3 MFMA loop (gemm_pp.hip, F8 = 1).  Scores are the fp32 sums of the exact
 //    products times a power-of-two score_scale; keys, foreign ids and select as above.
+//  * irc_rerank_topk_grouped ranks groups of rows (pages) instead of rows: after any of the
+//    four scoring passes rerank_collapse_kernel zeroes every key that is not the maximum of
+//    its (query, group) run, and the unchanged select returns the top-k distinct groups.
 #include <stdint.h>
 
 #include <cmath>
@@ -544,6 +547,197 @@ __global__ __launch_bounds__(RF_NT) void rerank_foreign_kernel(
     keys[i < pre ? c0 + i : lb + (i - pre)] = 0ull;
 }
 
+// The group of global row id: the g with group_off[g] <= id < group_off[g + 1] (upper
+// bound, so repeated offsets -- empty groups -- are stepped over), -1 for a row of no group.
+// The search starts from RC_NS samples of group_off the workgroup keeps in LDS -- s_first =
+// group_off[0], s_samp[t] = group_off[min((t + 1) * stride, n_groups)], so the last one is
+// group_off[n_groups] -- and only its last log2(stride) steps read global memory.
+constexpr int RC_NS = 256;
+__device__ __forceinline__ int group_of(const int64_t* __restrict__ group_off, int n_groups,
+                                        int64_t stride, int64_t s_first,
+                                        const int64_t* s_samp, int64_t id) {
+  if (n_groups <= 0 || id < s_first || id >= s_samp[RC_NS - 1]) return -1;
+  int c = 0, ch = RC_NS - 1;  // samples <= id: fewer than RC_NS, the last one is above id
+  while (c < ch) {
+    const int mid = (c + ch) >> 1;
+    if (s_samp[mid] <= id) c = mid + 1;
+    else ch = mid;
+  }
+  // group_off[c * stride] <= id < group_off[min((c + 1) * stride, n_groups)]
+  const int64_t top = (c + 1) * stride;
+  int lo = (int)(c * stride), hi = (int)(top < n_groups ? top : n_groups) - 1;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (group_off[mid + 1] <= id) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// Grouped top-k (irc_rerank_topk_grouped): between scoring and select, every key that is
+// not the maximum of its run becomes 0.  A run is a maximal stretch of consecutive
+// candidates of one query in one group (lists ascending); rows of no group are zeroed.
+// The same flat chunking as the scoring kernel, for any run length, in two phases:
+//  PHASE 0.  Every thread finds its owner and group and reads its own key, no other; a
+//    candidate whose left neighbour has another (owner, group) is a run head.  The kernel
+//    is bound by the latency of its dependent loads, so the group search starts in LDS
+//    (group_of) and the independent loads are issued before the owner search.  A max-scan
+//    of the head positions and a segmented max-scan of the keys run inside each wave
+//    (shuffles).  A run that begins and ends inside one wave -- nearly all of them at ten
+//    rows a page -- is settled there: the last lane's maximum goes back to the run's lanes
+//    and each zeroes its own key unless it is the maximum; head[i] = -1 marks it done.
+//    The other pieces (a run cut by a wave or chunk boundary) go through memory: head[i]
+//    keeps the flat index of the run's head -- from the earlier waves' tails through LDS,
+//    and for the run the chunk opens in, which may have begun chunks earlier, from one
+//    thread's binary search in the list for the first id of the group's row range -- and
+//    the last lane of each piece folds its maximum into rmax[head] with one 64-bit integer
+//    atomic max (rmax zeroed before the launch).  A run of any length, over any number of
+//    waves and chunks, ends with its maximum in its head's slot, whatever the order.
+//  PHASE 1 zeroes keys[i] unless head[i] < 0 or it equals rmax[head[i]].
+// In both phases a thread writes its own key only, and reads no other thread's key.
+// Keys are distinct (unique ids), so one key per run survives, and an all-zero run stays so.
+template <int PHASE>
+__global__ __launch_bounds__(RR_CHUNK) void rerank_collapse_kernel(
+    const int32_t* __restrict__ cand, const int64_t* __restrict__ cand_off, int Q,
+    int64_t n_cand, const int64_t* __restrict__ group_off, int n_groups,
+    uint64_t* __restrict__ keys, unsigned long long* __restrict__ rmax,
+    int64_t* __restrict__ head) {
+  const int tid = threadIdx.x;
+  const int64_t i0 = (int64_t)blockIdx.x * RR_CHUNK;
+  const int64_t i = i0 + tid;
+  if constexpr (PHASE == 1) {
+    if (i < n_cand) {
+      const int64_t h = head[i];
+      if (h >= 0) {
+        const uint64_t key = keys[i];
+        if (key != 0ull && key != (uint64_t)rmax[h]) keys[i] = 0ull;
+      }
+    }
+    return;
+  } else {
+    __shared__ int s_q[RR_CHUNK], s_g[RR_CHUNK];
+    __shared__ int s_wh[RR_CHUNK / 64];
+    __shared__ int64_t s_open, s_first;
+    __shared__ int64_t s_samp[RC_NS];
+    static_assert(RC_NS == RR_CHUNK, "one sample of group_off per thread");
+    const int lane = tid & 63, wave = tid >> 6;
+    const int64_t ilast = (i0 + RR_CHUNK <= n_cand ? i0 + RR_CHUNK : n_cand) - 1;
+    // every load that depends on nothing goes out first: the searches below are chains of
+    // dependent loads, and their length is what this kernel's time is made of
+    const bool valid = i < n_cand;
+    const int64_t id = valid ? (int64_t)cand[i] : 0;
+    const uint64_t own = valid ? keys[i] : 0ull;
+    const int64_t stride = ((int64_t)n_groups + RC_NS - 1) / RC_NS;
+    if (n_groups > 0) {
+      const int64_t at = (tid + 1) * stride;
+      s_samp[tid] = group_off[at < n_groups ? at : n_groups];
+      if (tid == 0) s_first = group_off[0];
+    }
+    // the chunk's first and last owner, then this thread's own (rerank_score_kernel)
+    int qa, qb;
+    {
+      int lo_a = 0, hi_a = Q, lo_b = 0, hi_b = Q;
+      while (lo_a < hi_a || lo_b < hi_b) {
+        if (lo_a < hi_a) {
+          const int mid = (lo_a + hi_a) >> 1;
+          if (cand_off[mid + 1] <= i0) lo_a = mid + 1;
+          else hi_a = mid;
+        }
+        if (lo_b < hi_b) {
+          const int mid = (lo_b + hi_b) >> 1;
+          if (cand_off[mid + 1] <= ilast) lo_b = mid + 1;
+          else hi_b = mid;
+        }
+      }
+      qa = lo_a;
+      qb = lo_b;
+    }
+    int myq = -1, myg = -1;  // past the end: a run of its own, no key
+    if (valid) {
+      myq = owner_of(cand_off, qa, qb, i);
+      myq = myq < Q - 1 ? myq : Q - 1;  // cand_off[Q] < n_cand (caller's error): stay in bounds
+    }
+    __syncthreads();  // the samples
+    if (valid) myg = group_of(group_off, n_groups, stride, s_first, s_samp, id);
+    const uint64_t key = myg >= 0 ? own : 0ull;  // a row of no group never wins
+    s_q[tid] = myq;
+    s_g[tid] = myg;
+    if (tid == 0) {
+      // the head of the run the chunk opens in: the list's first candidate of this group
+      // (its first id >= group_off[g]), searched in [list start, i0] only -- and no further
+      // back than the ids between the group's first row and this one allow (unique ids)
+      int64_t h = i0;
+      if (myg >= 0) {
+        const int64_t first = group_off[myg];
+        int64_t lo = cand_off[myq];
+        lo = lo < 0 ? 0 : lo;
+        lo = lo < i0 - (id - first) ? i0 - (id - first) : lo;
+        lo = lo < i0 ? lo : i0;
+        while (lo < h) {
+          const int64_t mid = lo + ((h - lo) >> 1);
+          if ((int64_t)cand[mid] < first) lo = mid + 1;
+          else h = mid;
+        }
+      }
+      s_open = h;
+    }
+    __syncthreads();
+    // a row of no group is a run of its own
+    const bool flag = tid == 0 || myg < 0 || s_q[tid - 1] != myq || s_g[tid - 1] != myg;
+    // the next candidate opens another run: known inside the chunk and at the end of keys[]
+    const bool nflag = tid < RR_CHUNK - 1
+                           ? (s_g[tid + 1] < 0 || s_q[tid + 1] != myq || s_g[tid + 1] != myg)
+                           : i + 1 >= n_cand;
+    const int64_t open = s_open;
+    // hl: the run head's place in the chunk as far as this wave knows it, -1: before the wave
+    int hl = flag ? tid : -1;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(hl, o, 64);
+      if (lane >= o) hl = t > hl ? t : hl;
+    }
+    // the run begins at that lane, not earlier (tid 0 only if the chunk opens a run)
+    const bool begins = hl > 0 || (hl == 0 && open == i0);
+    // segmented max inside the wave: lane - o is of this run while it is not before its head
+    const int sl = hl >= 0 ? hl - wave * 64 : 0;
+    uint64_t run = key;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint64_t t = __shfl_up(run, o, 64);
+      if (lane - o >= sl) run = t > run ? t : run;
+    }
+    const bool tail = lane == 63 || nflag;  // the last lane of this (run, wave) piece
+    int tl = tail ? lane : 64;              // that lane, for every lane of the piece
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_down(tl, o, 64);
+      if (lane + o < 64) tl = t < tl ? t : tl;
+    }
+    const uint64_t piece = __shfl(run, tl, 64);           // the piece's maximum
+    const bool ends = __shfl((int)nflag, tl, 64) != 0;    // the run ends with the piece
+    if (lane == 63) s_wh[wave] = hl;
+    __syncthreads();
+    if (begins && ends) {  // the whole run lies in this wave: settled here
+      if (valid) {
+        if (own != 0ull && own != piece) keys[i] = 0ull;
+        head[i] = -1;
+      }
+    } else {
+      if (hl < 0) {  // the run began in an earlier wave; wave 0 always knows (tid 0 is a head)
+        for (int v = wave - 1; v >= 0; --v) {
+          hl = s_wh[v];
+          if (hl >= 0) break;
+        }
+      }
+      const int64_t h = hl > 0 ? i0 + hl : open;  // in [0, i]
+      if (valid) {
+        head[i] = h;
+        if (tail && run != 0ull) atomicMax(&rmax[h], (unsigned long long)run);
+      }
+    }
+  }
+}
+
 static bool supported_d(int64_t D) {  // the scan's set (scan_topk.hip)
   return D == 64 || D == 128 || D == 256 || D == 384 || D == 512 || D == 768 || D == 1024;
 }
@@ -585,31 +779,11 @@ static int launch_select(const uint64_t* keys, const int64_t* cand_off, int64_t 
   return check_launch("rerank_select_kernel");
 }
 
-extern "C" int irc_rerank_topk(const void* queries, const void* docs, int64_t Q, int64_t N,
-                               int64_t D, const int32_t* cand, const int64_t* cand_off,
-                               int64_t n_cand, int64_t k, int64_t doc_offset, void* workspace,
-                               int64_t workspace_bytes, float* out_score, int64_t* out_idx,
-                               int32_t* out_n, irc_stream_t stream) {
-  IRC_REQUIRE(Q >= 0 && N >= 0 && n_cand >= 0, "rerank_topk: negative size");
-  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "rerank_topk: k=%lld outside [1, %d]", (long long)k,
-              RR_MAXK);
-  IRC_REQUIRE(supported_d(D), "rerank_topk: unsupported D=%lld", (long long)D);
-  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
-              "rerank_topk: global doc ids must fit int32 (doc_offset + N < 2^31)");
-  IRC_REQUIRE(Q < (1ll << 31) - 1, "rerank_topk: Q too large");
-  IRC_REQUIRE(n_cand < (1ll << 31) * RR_CHUNK, "rerank_topk: n_cand too large");
-  if (workspace == nullptr || workspace_bytes < (int64_t)workspace_bytes_for(n_cand)) {
-    set_error("rerank_topk: workspace %lld < required %lld bytes", (long long)workspace_bytes,
-              (long long)workspace_bytes_for(n_cand));
-    return IRC_E_WORKSPACE;
-  }
-  if (Q == 0) return IRC_OK;
-  IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n, "rerank_topk: null pointer");
-  IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)), "rerank_topk: null candidates / docs");
-  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
-              "rerank_topk: queries and docs must be 16-byte aligned");
-  hipStream_t st = as_stream(stream);
-  uint64_t* keys = static_cast<uint64_t*>(workspace);
+// The scoring passes, each filling keys[0 .. n_cand): the gathered rows (irc_rerank_topk),
+// the streamed shard (irc_rerank_topk_stream) and the two on e4m3 operands.
+static int score_gather(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,
+                        const int32_t* cand, const int64_t* cand_off, int64_t n_cand,
+                        int64_t doc_offset, uint64_t* keys, hipStream_t st) {
   if (n_cand > 0) {
     const unsigned blocks = (unsigned)((n_cand + RR_CHUNK - 1) / RR_CHUNK);
     const unsigned short* qp = static_cast<const unsigned short*>(queries);
@@ -633,39 +807,12 @@ extern "C" int irc_rerank_topk(const void* queries, const void* docs, int64_t Q,
     prof_end("rerank_score", st, (double)n_cand * D * 2.0);  // the gathered row bytes
     if (int rc = check_launch("rerank_score_kernel")) return rc;
   }
-  return launch_select(keys, cand_off, Q, n_cand, k, out_score, out_idx, out_n, st);
+  return IRC_OK;
 }
 
-extern "C" int irc_rerank_topk_stream(const void* queries, const void* docs, int64_t Q,
-                                      int64_t N, int64_t D, const int32_t* cand,
-                                      const int64_t* cand_off, int64_t n_cand, int64_t k,
-                                      int64_t doc_offset, void* workspace,
-                                      int64_t workspace_bytes, float* out_score,
-                                      int64_t* out_idx, int32_t* out_n, irc_stream_t stream) {
-  // irc_rerank_topk's checks, in its order
-  IRC_REQUIRE(Q >= 0 && N >= 0 && n_cand >= 0, "rerank_topk: negative size");
-  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "rerank_topk: k=%lld outside [1, %d]", (long long)k,
-              RR_MAXK);
-  IRC_REQUIRE(supported_d(D), "rerank_topk: unsupported D=%lld", (long long)D);
-  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
-              "rerank_topk: global doc ids must fit int32 (doc_offset + N < 2^31)");
-  IRC_REQUIRE(Q < (1ll << 31) - 1, "rerank_topk: Q too large");
-  IRC_REQUIRE(n_cand < (1ll << 31) * RR_CHUNK, "rerank_topk: n_cand too large");
-  // one workgroup per (query tile, doc tile): the grid and the kernel's int tile count
-  IRC_REQUIRE(((Q + 255) / 256) * ((N + 255) / 256) < (1ll << 31),
-              "rerank_topk: Q x N too large for the stream method");
-  if (workspace == nullptr || workspace_bytes < (int64_t)workspace_bytes_for(n_cand)) {
-    set_error("rerank_topk: workspace %lld < required %lld bytes", (long long)workspace_bytes,
-              (long long)workspace_bytes_for(n_cand));
-    return IRC_E_WORKSPACE;
-  }
-  if (Q == 0) return IRC_OK;
-  IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n, "rerank_topk: null pointer");
-  IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)), "rerank_topk: null candidates / docs");
-  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
-              "rerank_topk: queries and docs must be 16-byte aligned");
-  hipStream_t st = as_stream(stream);
-  uint64_t* keys = static_cast<uint64_t*>(workspace);
+static int score_stream(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,
+                        const int32_t* cand, const int64_t* cand_off, int64_t n_cand,
+                        int64_t doc_offset, uint64_t* keys, hipStream_t st) {
   if (n_cand > 0) {
     prof_begin(st);
     hipLaunchKernelGGL(rerank_foreign_kernel, dim3((unsigned)Q, RF_Y), dim3(RF_NT), 0, st, cand,
@@ -691,44 +838,12 @@ extern "C" int irc_rerank_topk_stream(const void* queries, const void* docs, int
     prof_end("rerank_stream_score", st, (double)((Q + 255) / 256) * (double)N * D * 2.0);
     if (int rc = check_launch("rerank_stream_score")) return rc;
   }
-  return launch_select(keys, cand_off, Q, n_cand, k, out_score, out_idx, out_n, st);
+  return IRC_OK;
 }
 
-// The two e4m3 entries: irc_rerank_topk's checks in its order, the e4m3 ones after the D
-// check, then one of the two scoring passes and the shared select.
-static int rerank_fp8_impl(bool stream, const void* queries, const void* docs, int64_t Q,
-                           int64_t N, int64_t D, const int32_t* cand, const int64_t* cand_off,
-                           int64_t n_cand, int64_t k, int64_t doc_offset, float score_scale,
-                           void* workspace, int64_t workspace_bytes, float* out_score,
-                           int64_t* out_idx, int32_t* out_n, irc_stream_t stream_) {
-  IRC_REQUIRE(Q >= 0 && N >= 0 && n_cand >= 0, "rerank_topk_fp8: negative size");
-  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "rerank_topk_fp8: k=%lld outside [1, %d]", (long long)k,
-              RR_MAXK);
-  IRC_REQUIRE(supported_d(D), "rerank_topk_fp8: unsupported D=%lld", (long long)D);
-  IRC_REQUIRE(!stream || D % 128 == 0,
-              "rerank_topk_fp8: unsupported D=%lld for the stream method (D %% 128 == 0)",
-              (long long)D);
-  IRC_REQUIRE(pow2_scale(score_scale), "rerank_topk_fp8: score_scale must be a power of two");
-  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
-              "rerank_topk_fp8: global doc ids must fit int32 (doc_offset + N < 2^31)");
-  IRC_REQUIRE(Q < (1ll << 31) - 1, "rerank_topk_fp8: Q too large");
-  IRC_REQUIRE(n_cand < (1ll << 31) * RR_CHUNK, "rerank_topk_fp8: n_cand too large");
-  IRC_REQUIRE(!stream || ((Q + 255) / 256) * ((N + 255) / 256) < (1ll << 31),
-              "rerank_topk_fp8: Q x N too large for the stream method");
-  if (workspace == nullptr || workspace_bytes < (int64_t)workspace_bytes_for(n_cand)) {
-    set_error("rerank_topk_fp8: workspace %lld < required %lld bytes", (long long)workspace_bytes,
-              (long long)workspace_bytes_for(n_cand));
-    return IRC_E_WORKSPACE;
-  }
-  if (Q == 0) return IRC_OK;
-  IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n,
-              "rerank_topk_fp8: null pointer");
-  IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)),
-              "rerank_topk_fp8: null candidates / docs");
-  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
-              "rerank_topk_fp8: queries and docs must be 16-byte aligned");
-  hipStream_t st = as_stream(stream_);
-  uint64_t* keys = static_cast<uint64_t*>(workspace);
+static int score_fp8(bool stream, const void* queries, const void* docs, int64_t Q, int64_t N,
+                     int64_t D, const int32_t* cand, const int64_t* cand_off, int64_t n_cand,
+                     int64_t doc_offset, float score_scale, uint64_t* keys, hipStream_t st) {
   if (n_cand > 0 && !stream) {
     const unsigned blocks = (unsigned)((n_cand + RR_CHUNK - 1) / RR_CHUNK);
     const unsigned char* qp = static_cast<const unsigned char*>(queries);
@@ -778,6 +893,112 @@ static int rerank_fp8_impl(bool stream, const void* queries, const void* docs, i
     prof_end("rerank_fp8_stream_score", st, (double)((Q + 255) / 256) * (double)N * D);
     if (int rc = check_launch("rerank_fp8_stream_score")) return rc;
   }
+  return IRC_OK;
+}
+
+extern "C" int irc_rerank_topk(const void* queries, const void* docs, int64_t Q, int64_t N,
+                               int64_t D, const int32_t* cand, const int64_t* cand_off,
+                               int64_t n_cand, int64_t k, int64_t doc_offset, void* workspace,
+                               int64_t workspace_bytes, float* out_score, int64_t* out_idx,
+                               int32_t* out_n, irc_stream_t stream) {
+  IRC_REQUIRE(Q >= 0 && N >= 0 && n_cand >= 0, "rerank_topk: negative size");
+  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "rerank_topk: k=%lld outside [1, %d]", (long long)k,
+              RR_MAXK);
+  IRC_REQUIRE(supported_d(D), "rerank_topk: unsupported D=%lld", (long long)D);
+  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
+              "rerank_topk: global doc ids must fit int32 (doc_offset + N < 2^31)");
+  IRC_REQUIRE(Q < (1ll << 31) - 1, "rerank_topk: Q too large");
+  IRC_REQUIRE(n_cand < (1ll << 31) * RR_CHUNK, "rerank_topk: n_cand too large");
+  if (workspace == nullptr || workspace_bytes < (int64_t)workspace_bytes_for(n_cand)) {
+    set_error("rerank_topk: workspace %lld < required %lld bytes", (long long)workspace_bytes,
+              (long long)workspace_bytes_for(n_cand));
+    return IRC_E_WORKSPACE;
+  }
+  if (Q == 0) return IRC_OK;
+  IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n, "rerank_topk: null pointer");
+  IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)), "rerank_topk: null candidates / docs");
+  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
+              "rerank_topk: queries and docs must be 16-byte aligned");
+  hipStream_t st = as_stream(stream);
+  uint64_t* keys = static_cast<uint64_t*>(workspace);
+  if (int rc = score_gather(queries, docs, Q, N, D, cand, cand_off, n_cand, doc_offset, keys, st))
+    return rc;
+  return launch_select(keys, cand_off, Q, n_cand, k, out_score, out_idx, out_n, st);
+}
+
+extern "C" int irc_rerank_topk_stream(const void* queries, const void* docs, int64_t Q,
+                                      int64_t N, int64_t D, const int32_t* cand,
+                                      const int64_t* cand_off, int64_t n_cand, int64_t k,
+                                      int64_t doc_offset, void* workspace,
+                                      int64_t workspace_bytes, float* out_score,
+                                      int64_t* out_idx, int32_t* out_n, irc_stream_t stream) {
+  // irc_rerank_topk's checks, in its order
+  IRC_REQUIRE(Q >= 0 && N >= 0 && n_cand >= 0, "rerank_topk: negative size");
+  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "rerank_topk: k=%lld outside [1, %d]", (long long)k,
+              RR_MAXK);
+  IRC_REQUIRE(supported_d(D), "rerank_topk: unsupported D=%lld", (long long)D);
+  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
+              "rerank_topk: global doc ids must fit int32 (doc_offset + N < 2^31)");
+  IRC_REQUIRE(Q < (1ll << 31) - 1, "rerank_topk: Q too large");
+  IRC_REQUIRE(n_cand < (1ll << 31) * RR_CHUNK, "rerank_topk: n_cand too large");
+  // one workgroup per (query tile, doc tile): the grid and the kernel's int tile count
+  IRC_REQUIRE(((Q + 255) / 256) * ((N + 255) / 256) < (1ll << 31),
+              "rerank_topk: Q x N too large for the stream method");
+  if (workspace == nullptr || workspace_bytes < (int64_t)workspace_bytes_for(n_cand)) {
+    set_error("rerank_topk: workspace %lld < required %lld bytes", (long long)workspace_bytes,
+              (long long)workspace_bytes_for(n_cand));
+    return IRC_E_WORKSPACE;
+  }
+  if (Q == 0) return IRC_OK;
+  IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n, "rerank_topk: null pointer");
+  IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)), "rerank_topk: null candidates / docs");
+  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
+              "rerank_topk: queries and docs must be 16-byte aligned");
+  hipStream_t st = as_stream(stream);
+  uint64_t* keys = static_cast<uint64_t*>(workspace);
+  if (int rc = score_stream(queries, docs, Q, N, D, cand, cand_off, n_cand, doc_offset, keys, st))
+    return rc;
+  return launch_select(keys, cand_off, Q, n_cand, k, out_score, out_idx, out_n, st);
+}
+
+// The two e4m3 entries: irc_rerank_topk's checks in its order, the e4m3 ones after the D
+// check, then one of the two scoring passes and the shared select.
+static int rerank_fp8_impl(bool stream, const void* queries, const void* docs, int64_t Q,
+                           int64_t N, int64_t D, const int32_t* cand, const int64_t* cand_off,
+                           int64_t n_cand, int64_t k, int64_t doc_offset, float score_scale,
+                           void* workspace, int64_t workspace_bytes, float* out_score,
+                           int64_t* out_idx, int32_t* out_n, irc_stream_t stream_) {
+  IRC_REQUIRE(Q >= 0 && N >= 0 && n_cand >= 0, "rerank_topk_fp8: negative size");
+  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "rerank_topk_fp8: k=%lld outside [1, %d]", (long long)k,
+              RR_MAXK);
+  IRC_REQUIRE(supported_d(D), "rerank_topk_fp8: unsupported D=%lld", (long long)D);
+  IRC_REQUIRE(!stream || D % 128 == 0,
+              "rerank_topk_fp8: unsupported D=%lld for the stream method (D %% 128 == 0)",
+              (long long)D);
+  IRC_REQUIRE(pow2_scale(score_scale), "rerank_topk_fp8: score_scale must be a power of two");
+  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
+              "rerank_topk_fp8: global doc ids must fit int32 (doc_offset + N < 2^31)");
+  IRC_REQUIRE(Q < (1ll << 31) - 1, "rerank_topk_fp8: Q too large");
+  IRC_REQUIRE(n_cand < (1ll << 31) * RR_CHUNK, "rerank_topk_fp8: n_cand too large");
+  IRC_REQUIRE(!stream || ((Q + 255) / 256) * ((N + 255) / 256) < (1ll << 31),
+              "rerank_topk_fp8: Q x N too large for the stream method");
+  if (workspace == nullptr || workspace_bytes < (int64_t)workspace_bytes_for(n_cand)) {
+    set_error("rerank_topk_fp8: workspace %lld < required %lld bytes", (long long)workspace_bytes,
+              (long long)workspace_bytes_for(n_cand));
+    return IRC_E_WORKSPACE;
+  }
+  if (Q == 0) return IRC_OK;
+  IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n,
+              "rerank_topk_fp8: null pointer");
+  IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)),
+              "rerank_topk_fp8: null candidates / docs");
+  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
+              "rerank_topk_fp8: queries and docs must be 16-byte aligned");
+  hipStream_t st = as_stream(stream_);
+  uint64_t* keys = static_cast<uint64_t*>(workspace);
+  if (int rc = score_fp8(stream, queries, docs, Q, N, D, cand, cand_off, n_cand, doc_offset,
+                         score_scale, keys, st))
+    return rc;
   return launch_select(keys, cand_off, Q, n_cand, k, out_score, out_idx, out_n, st);
 }
 
@@ -802,4 +1023,89 @@ extern "C" int irc_rerank_topk_stream_fp8(const void* queries, const void* docs,
   return rerank_fp8_impl(true, queries, docs, Q, N, D, cand, cand_off, n_cand, k, doc_offset,
                          score_scale, workspace, workspace_bytes, out_score, out_idx, out_n,
                          stream);
+}
+
+// keys | rmax | head, each region aligned as irc_rerank_topk's one
+static size_t grouped_region_bytes(int64_t n_cand) {
+  return (((size_t)(n_cand > 0 ? n_cand : 0) * 8) + 255) & ~(size_t)255;
+}
+
+extern "C" int64_t irc_rerank_topk_grouped_workspace(int64_t Q, int64_t n_cand, int64_t k) {
+  (void)Q;
+  (void)k;
+  return (int64_t)(3 * grouped_region_bytes(n_cand) + 256);
+}
+
+// The top-k per group: irc_rerank_topk's checks in its order (the stream and e4m3 ones where
+// those entries have them), the group checks last; one of the four scoring passes, the two
+// collapse phases, the shared select.
+extern "C" int irc_rerank_topk_grouped(const void* queries, const void* docs, int64_t Q,
+                                       int64_t N, int64_t D, const int32_t* cand,
+                                       const int64_t* cand_off, int64_t n_cand, int64_t k,
+                                       int64_t doc_offset, const int64_t* group_off,
+                                       int64_t n_groups, uint32_t flags, float score_scale,
+                                       void* workspace, int64_t workspace_bytes,
+                                       float* out_score, int64_t* out_idx, int32_t* out_n,
+                                       irc_stream_t stream_) {
+  const bool stream = (flags & IRC_RERANK_STREAM) != 0, e4m3 = (flags & IRC_RERANK_E4M3) != 0;
+  IRC_REQUIRE(Q >= 0 && N >= 0 && n_cand >= 0, "rerank_topk_grouped: negative size");
+  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "rerank_topk_grouped: k=%lld outside [1, %d]",
+              (long long)k, RR_MAXK);
+  IRC_REQUIRE(supported_d(D), "rerank_topk_grouped: unsupported D=%lld", (long long)D);
+  IRC_REQUIRE(!(e4m3 && stream) || D % 128 == 0,
+              "rerank_topk_grouped: unsupported D=%lld for the e4m3 stream method "
+              "(D %% 128 == 0)", (long long)D);
+  IRC_REQUIRE(!e4m3 || pow2_scale(score_scale),
+              "rerank_topk_grouped: score_scale must be a power of two");
+  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
+              "rerank_topk_grouped: global doc ids must fit int32 (doc_offset + N < 2^31)");
+  IRC_REQUIRE(Q < (1ll << 31) - 1, "rerank_topk_grouped: Q too large");
+  IRC_REQUIRE(n_cand < (1ll << 31) * RR_CHUNK, "rerank_topk_grouped: n_cand too large");
+  IRC_REQUIRE(!stream || ((Q + 255) / 256) * ((N + 255) / 256) < (1ll << 31),
+              "rerank_topk_grouped: Q x N too large for the stream method");
+  const int64_t need = irc_rerank_topk_grouped_workspace(Q, n_cand, k);
+  if (workspace == nullptr || workspace_bytes < need) {
+    set_error("rerank_topk_grouped: workspace %lld < required %lld bytes",
+              (long long)workspace_bytes, (long long)need);
+    return IRC_E_WORKSPACE;
+  }
+  if (Q == 0) return IRC_OK;
+  IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n,
+              "rerank_topk_grouped: null pointer");
+  IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)),
+              "rerank_topk_grouped: null candidates / docs");
+  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
+              "rerank_topk_grouped: queries and docs must be 16-byte aligned");
+  IRC_REQUIRE(group_off != nullptr, "rerank_topk_grouped: null group_off");
+  IRC_REQUIRE(n_groups >= 0 && n_groups < (1ll << 31) - 1,
+              "rerank_topk_grouped: n_groups=%lld outside [0, 2^31 - 1)", (long long)n_groups);
+  hipStream_t st = as_stream(stream_);
+  const size_t region = grouped_region_bytes(n_cand);
+  uint64_t* keys = static_cast<uint64_t*>(workspace);
+  unsigned long long* rmax =
+      reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + region);
+  int64_t* head = reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + 2 * region);
+  int rc;
+  if (e4m3)
+    rc = score_fp8(stream, queries, docs, Q, N, D, cand, cand_off, n_cand, doc_offset,
+                   score_scale, keys, st);
+  else if (stream)
+    rc = score_stream(queries, docs, Q, N, D, cand, cand_off, n_cand, doc_offset, keys, st);
+  else
+    rc = score_gather(queries, docs, Q, N, D, cand, cand_off, n_cand, doc_offset, keys, st);
+  if (rc) return rc;
+  if (n_cand > 0) {
+    const unsigned blocks = (unsigned)((n_cand + RR_CHUNK - 1) / RR_CHUNK);
+    if (hipMemsetAsync(rmax, 0, (size_t)n_cand * 8, st) != hipSuccess)
+      return check_launch("rerank_collapse memset");
+    prof_begin(st);
+    hipLaunchKernelGGL((rerank_collapse_kernel<0>), dim3(blocks), dim3(RR_CHUNK), 0, st, cand,
+                       cand_off, (int)Q, n_cand, group_off, (int)n_groups, keys, rmax, head);
+    hipLaunchKernelGGL((rerank_collapse_kernel<1>), dim3(blocks), dim3(RR_CHUNK), 0, st, cand,
+                       cand_off, (int)Q, n_cand, group_off, (int)n_groups, keys, rmax, head);
+    // per key: key + id read, head written, then key + head + slot read
+    prof_end("rerank_collapse", st, (double)n_cand * 44.0);
+    if (int rc2 = check_launch("rerank_collapse_kernel")) return rc2;
+  }
+  return launch_select(keys, cand_off, Q, n_cand, k, out_score, out_idx, out_n, st);
 }

@@ -19,6 +19,7 @@ _c = ctypes
 P = _c.c_void_p
 I64 = _c.c_int64
 I32 = _c.c_int
+U32 = _c.c_uint32
 F32 = _c.c_float
 
 # name -> (restype, argtypes).  Keep in sync with include/irc.h
@@ -48,6 +49,9 @@ SIGNATURES = {
                                   P]),
     "irc_rerank_topk_stream_fp8": (I32, [P, P, I64, I64, I64, P, P, I64, I64, I64, F32, P, I64, P,
                                          P, P, P]),
+    "irc_rerank_topk_grouped_workspace": (I64, [I64, I64, I64]),
+    "irc_rerank_topk_grouped": (I32, [P, P, I64, I64, I64, P, P, I64, I64, I64, P, I64, U32, F32,
+                                      P, I64, P, P, P, P]),
     "irc_scan_topk_fp8_workspace": (I64, [I64, I64, I64, I64]),
     "irc_scan_topk_fp8": (I32, [P, P, I64, I64, I64, I64, I64, F32, P, I64, P, P, P]),
     "irc_scan_scores_fp8": (I32, [P, P, I64, I64, I64, P, P]),

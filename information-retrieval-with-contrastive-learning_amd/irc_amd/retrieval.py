@@ -259,9 +259,28 @@ def _sort_lists(cand: torch.Tensor, cand_off: torch.Tensor) -> torch.Tensor:
     return ((key & 0xFFFFFFFF) - 2 ** 31).to(torch.int32)
 
 
+RERANK_FLAG_STREAM = 1  # irc.h: IRC_RERANK_STREAM
+RERANK_FLAG_E4M3 = 2  # irc.h: IRC_RERANK_E4M3
+
+
+def _check_group_off(group_off, queries):
+    """The ``group_off`` argument of the rerank calls, checked before anything else runs:
+    1-D int64 with at least one entry, on the queries' device."""
+    if group_off is None:
+        return
+    if not isinstance(group_off, torch.Tensor) or group_off.dtype != torch.int64:
+        raise TypeError("group_off must be an int64 tensor, not "
+                        f"{getattr(group_off, 'dtype', type(group_off))}")
+    if group_off.dim() != 1 or group_off.numel() < 1:
+        raise ValueError("group_off must be 1-D with n_groups + 1 >= 1 entries, not shape "
+                         f"{tuple(group_off.shape)}")
+    if group_off.device != queries.device:
+        raise ValueError(f"group_off is on {group_off.device}, the queries on {queries.device}")
+
+
 def rerank_topk(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
                 cand_off: torch.Tensor, k: int, doc_offset: int = 0, ws_tag: str = "rerank",
-                method: str = "gather", ascending: bool = False):
+                method: str = "gather", ascending: bool = False, group_off=None):
     """Exact top-k of each query over ITS OWN candidate docs (sparse filter, dense rerank:
     src/evaluation.py:57-83 feeding :110-112).
 
@@ -283,68 +302,104 @@ def rerank_topk(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
     ``expand_ranges`` leave them so); otherwise they are sorted on the device first (one
     ``torch.sort``, no host synchronisation) and the result is the same.  Under "stream"
     an int64 id outside int32 is clamped to -1 / 2^31 - 1, which no shard owns, so an
-    ascending list stays ascending."""
+    ascending list stays ascending.
+
+    ``group_off`` (int64 [n_groups + 1] on the queries' device, non-decreasing, in GLOBAL
+    row ids whatever ``doc_offset``): the top-k per group instead of per row
+    (irc_rerank_topk_grouped).  Group g owns the rows [group_off[g], group_off[g + 1]);
+    each query's candidates collapse to the best row of every group -- equal scores keep
+    the lower id -- and the call returns (scores, idx, n, groups): the top-k distinct
+    groups, each by its best row, n[q] = min(k, groups with an eligible row), and groups
+    int64 [Q, k] the group of each returned row (-1 in padded slots).  A row outside
+    [group_off[0], group_off[-1]) is in no group and never returned.  The collapse needs
+    ascending lists under both methods, so without ``ascending=True`` the lists are sorted
+    first under "gather" too.  It happens inside this one shard: a group whose rows lie
+    in two shards yields one winner per shard, and merging grouped results of several
+    shards is not built.  With ``group_off=None`` nothing changes."""
     if method not in RERANK_METHODS:
         raise ValueError(f"method must be one of {RERANK_METHODS}, not {method!r}")
+    _check_group_off(group_off, queries)
     require_hip(queries, docs, cand, cand_off)
     q = contig(queries, torch.bfloat16)
     d = contig(docs, torch.bfloat16)
     if d.shape[1] != q.shape[1]:
         raise ValueError(f"dim mismatch: queries D={q.shape[1]}, docs D={d.shape[1]}")
     entry = "irc_rerank_topk_stream" if method == "stream" else "irc_rerank_topk"
-    return _rerank_call(entry, (), q, d, cand, cand_off, k, doc_offset, ws_tag, method, ascending)
+    return _rerank_call(entry, (), q, d, cand, cand_off, k, doc_offset, ws_tag, method, ascending,
+                        group_off)
 
 
-def _rerank_call(entry, extra, q, d, cand, cand_off, k, doc_offset, ws_tag, method, ascending):
+def _rerank_call(entry, extra, q, d, cand, cand_off, k, doc_offset, ws_tag, method, ascending,
+                 group_off=None):
     """The part of ``rerank_topk`` and ``rerank_topk_fp8`` after their operand checks: the
     id handling, the sort under "stream", the outputs and the native call (``extra``: the
-    entry's arguments between doc_offset and the workspace)."""
+    entry's arguments between doc_offset and the workspace).  With ``group_off`` the one
+    grouped entry takes the place of ``entry``: the scoring form goes in its flags word,
+    ``extra`` (the e4m3 entries' score_scale) in its score_scale."""
     Q, D = q.shape
     N = d.shape[0]
+    grouped = group_off is not None
+    ordered = grouped or method == "stream"  # the kernels need ascending lists
     if cand.dtype not in (torch.int32, torch.int64):
         raise TypeError(f"cand must be int32 or int64, not {cand.dtype}")
     if cand_off.numel() != Q + 1:
         raise ValueError(f"cand_off has {cand_off.numel()} entries for {Q} queries (Q + 1)")
     if cand.dtype == torch.int64:
         # an id outside int32 is in no shard (doc_offset + N < 2^31): it must not wrap into one
-        if method == "stream":  # order-preserving
+        if ordered:  # order-preserving
             cand = cand.clamp(-1, 2 ** 31 - 1)
         else:
             cand = torch.where((cand < 0) | (cand >= 2 ** 31), cand.new_full((), -1), cand)
     off = contig(cand_off, torch.int64)
-    if method == "stream" and not ascending:
+    if ordered and not ascending:
         cand = _sort_lists(cand.reshape(-1), off)
     c = contig(cand, torch.int32)
     n_cand = c.numel()
     out_s = torch.empty((Q, k), dtype=torch.float32, device=q.device)
     out_i = torch.empty((Q, k), dtype=torch.int64, device=q.device)
     out_n = torch.empty((Q,), dtype=torch.int32, device=q.device)
-    nbytes = int(_lib.fn("irc_rerank_topk_workspace")(Q, n_cand, k))
+    if not grouped:
+        nbytes = int(_lib.fn("irc_rerank_topk_workspace")(Q, n_cand, k))
+        ws = workspace(nbytes, q.device, ws_tag)
+        _lib.call(entry, ptr(q), ptr(d), Q, N, D, ptr(c), ptr(off), n_cand, k,
+                  doc_offset, *extra, ptr(ws), ws.numel(), ptr(out_s), ptr(out_i), ptr(out_n),
+                  stream_ptr(q.device))
+        return out_s, out_i, out_n
+    go = group_off.contiguous()
+    n_groups = go.numel() - 1
+    flags = (RERANK_FLAG_STREAM if method == "stream" else 0) | \
+        (RERANK_FLAG_E4M3 if q.dtype == torch.uint8 else 0)
+    score_scale = float(extra[0]) if extra else 1.0
+    nbytes = int(_lib.fn("irc_rerank_topk_grouped_workspace")(Q, n_cand, k))
     ws = workspace(nbytes, q.device, ws_tag)
-    _lib.call(entry, ptr(q), ptr(d), Q, N, D, ptr(c), ptr(off), n_cand, k,
-              doc_offset, *extra, ptr(ws), ws.numel(), ptr(out_s), ptr(out_i), ptr(out_n),
-              stream_ptr(q.device))
-    return out_s, out_i, out_n
+    _lib.call("irc_rerank_topk_grouped", ptr(q), ptr(d), Q, N, D, ptr(c), ptr(off), n_cand, k,
+              doc_offset, ptr(go), n_groups, flags, score_scale, ptr(ws), ws.numel(),
+              ptr(out_s), ptr(out_i), ptr(out_n), stream_ptr(q.device))
+    # every returned row lies in [group_off[0], group_off[-1]); a padded slot is -1
+    groups = torch.searchsorted(go, out_i, right=True) - 1
+    groups = torch.where(out_i < 0, groups.new_full((), -1), groups)
+    return out_s, out_i, out_n, groups
 
 
 def rerank_topk_fp8(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
                     cand_off: torch.Tensor, k: int, doc_offset: int = 0,
                     score_scale: float = 1.0, ws_tag: str = "rerank", method: str = "gather",
-                    ascending: bool = False):
+                    ascending: bool = False, group_off=None):
     """``rerank_topk`` over e4m3 operands: queries [Q, D] and docs [N, D] are uint8 codes
     (``quantize_fp8``).  The scores are the fp32 dot products of the decoded values times
     ``score_scale`` (a power of two), as ``scan_topk_fp8`` reports them; candidates, ids,
-    ``method``, ``ascending`` and the outputs are ``rerank_topk``'s.  "gather" is
-    irc_rerank_topk_fp8, "stream" irc_rerank_topk_stream_fp8 (D % 128 == 0); on values
+    ``method``, ``ascending``, ``group_off`` and the outputs are ``rerank_topk``'s.  "gather"
+    is irc_rerank_topk_fp8, "stream" irc_rerank_topk_stream_fp8 (D % 128 == 0); on values
     whose sums are exact in fp32 the two agree bitwise."""
     if method not in RERANK_METHODS:
         raise ValueError(f"method must be one of {RERANK_METHODS}, not {method!r}")
+    _check_group_off(group_off, queries)
     _require_e4m3(queries, docs)  # a wrong dtype is a TypeError on any device
     q, d = _fp8_operands(queries, docs)
     require_hip(cand, cand_off)
     entry = "irc_rerank_topk_stream_fp8" if method == "stream" else "irc_rerank_topk_fp8"
     return _rerank_call(entry, (float(score_scale),), q, d, cand, cand_off, k, doc_offset, ws_tag,
-                        method, ascending)
+                        method, ascending, group_off)
 
 
 def expand_ranges(cand: torch.Tensor, cand_off: torch.Tensor, row_off: torch.Tensor):
@@ -475,7 +530,7 @@ class ShardedDenseIndex:
 
     def search_candidates(self, queries: torch.Tensor, cand: torch.Tensor,
                           cand_off: torch.Tensor, k: int, ws_tag: str = "rerank",
-                          method: str = "gather", ascending: bool = False):
+                          method: str = "gather", ascending: bool = False, group_off=None):
         """Top-k of each query over its own candidate docs only (global ids, the CSR pair
         ``SparseIndex.candidates`` / ``expand_ranges`` leave on the device): (scores
         [Q, k], idx [Q, k], n [Q]) as ``rerank_topk``.  Single process; bf16 and fp8 shards
@@ -486,6 +541,12 @@ class ShardedDenseIndex:
         ``method``: "gather" (the default), "stream", or "auto", which takes
         ``rerank_method``'s choice when ``ascending=True`` and "gather" otherwise;
         ``ascending`` as in ``rerank_topk``.
+
+        ``group_off`` (int64 [n_groups + 1], global row ids, on the queries' device): the
+        top-k distinct groups, each by its best row, and a fourth result ``groups`` [Q, k],
+        as ``rerank_topk`` documents it; "auto" chooses as without it.  The collapse
+        happens inside this one shard: a group whose rows lie in two shards yields one
+        winner per shard (the multi-shard merge of grouped results is not built).
 
         Cost model: "gather" reads the candidate rows whole, once per
         (query, candidate), with no reuse across queries -- n_cand * D * 2 bytes -- while
@@ -520,6 +581,7 @@ class ShardedDenseIndex:
         5.8 % at Q = 16, and above 25 % at Q = 1.  The scoring pass gathers 4.8-7.6 TB/s of
         row bytes from 160k candidates up (lists of one call that overlap hit the caches)
         and is latency-bound below."""
+        _check_group_off(group_off, queries)
         if self.dtype == "fp8" and self.docs.dtype != torch.uint8:
             # before anything touches the queries or the device: a hand-built index or a
             # damaged header on load()
@@ -539,9 +601,9 @@ class ShardedDenseIndex:
             q8 = quantize_fp8(queries, self.fp8_scale)
             return rerank_topk_fp8(q8, self.docs, cand, cand_off, k, self.doc_offset,
                                    1.0 / (self.fp8_scale * self.fp8_scale), ws_tag=ws_tag,
-                                   method=method, ascending=ascending)
+                                   method=method, ascending=ascending, group_off=group_off)
         return rerank_topk(queries, self.docs, cand, cand_off, k, self.doc_offset, ws_tag=ws_tag,
-                           method=method, ascending=ascending)
+                           method=method, ascending=ascending, group_off=group_off)
 
     # The three steps of a sharded search, separately callable (bench.py times each).
     def _sharded(self):

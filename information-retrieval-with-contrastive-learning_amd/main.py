@@ -3,7 +3,8 @@
     python main.py [--config config.yaml] [--data doc|fever] [--gpu 0] [--ckpt X]
                    [--model LSTM|BERT] [--loss InfoNCE] [--opt adam] [--sample uniform|tf_idf]
                    [--seed 1337] [--logdir log] [--ckptdir ckpt] [--retrieval sparse|dense|hybrid]
-                   [--rerank-method auto|gather|stream] [--index-dtype bf16|fp8]
+                   [--rerank-method auto|gather|stream] [--rerank-unit line|page]
+                   [--index-dtype bf16|fp8]
 
 Multi-GPU (one process per GPU):
     torchrun --nproc-per-node N --master-addr 127.0.0.1 main.py [same flags]
@@ -18,7 +19,9 @@ shards the evidence corpus over the ranks.  IRC_DIST_BACKEND=gloo selects gloo
 the reference's sparse candidate filter per claim (default) or, with
 ``--retrieval dense``, the bi-encoder's exact top-k over the evidence corpus, or, with
 ``--retrieval hybrid``, that top-k over each claim's filter candidates only (the
-reference's two stages joined; single process).  The compute runs on the MI355X HIP kernels only:
+reference's two stages joined; single process; ``--rerank-unit page`` ranks the k best
+pages, each by its best line, instead of the k best lines).  The compute runs on the
+MI355X HIP kernels only:
 ``--gpu -1`` (CPU) is rejected -- there is no CPU fallback in this build.
 """
 import argparse
@@ -68,6 +71,12 @@ def get_args(argv=None):
                         "crossovers. Same ranking contract either way: the exact top-k over "
                         "the candidates only; scores may differ in the last bits (another "
                         "fp32 summation order)")
+    p.add_argument("--rerank-unit", default="line", type=str, choices=["line", "page"],
+                   help="--retrieval hybrid: what the top-k counts. line (default): the k "
+                        "best evidence lines, several of which may be of one page. page: the "
+                        "k best pages, each by its best line (ties: the earlier line), "
+                        "collapsed on the device before the select; the printed recall is "
+                        "then over k pages")
     p.add_argument("--index-dtype", default="bf16", type=str, choices=["bf16", "fp8"],
                    help="--retrieval dense / hybrid: how the evidence corpus is kept in HBM. "
                         "bf16 (default), or fp8: e4m3 bytes at half the size, the claims "

@@ -170,20 +170,25 @@ def hybrid_corpus(wiki, doc_ids):
 
 @torch.no_grad()
 def hybrid_search(model, dense_index, sparse_index, row_off, claims, k, device,
-                  bigram_only=False, method="gather"):
+                  bigram_only=False, method="gather", group_off=None):
     """Sparse filter, dense rerank for a batch of claims (src/evaluation.py:57-83 feeding
     :110-112), all on the device: the claims' candidate columns (SparseIndex.candidates)
     expanded to their evidence rows (``row_off``, int64 [n_cols + 1] on the device) and
     each claim's ``ctx2vec`` embedding ranked against its own rows only.  Returns
     (scores [Q, k], idx [Q, k] corpus rows, n [Q]) as rerank_topk.  ``method``: "gather",
     "stream" or "auto" (``ShardedDenseIndex.search_candidates``); the row lists are
-    ascending by construction, which the stream method needs."""
+    ascending by construction, which the stream method needs.  ``group_off`` (int64
+    [n_groups + 1] on the device; ``row_off`` itself for pages): the top-k distinct groups,
+    each by its best row, and a fourth value groups [Q, k] (``rerank_topk``)."""
     from irc_amd.retrieval import expand_ranges
 
     q = model.ctx2vec(claims, device)
     cand, off = sparse_index.candidates(claims, bigram_only)
     rows, rows_off = expand_ranges(cand, off, row_off)
-    return dense_index.search_candidates(q, rows, rows_off, k, method=method, ascending=True)
+    if group_off is None:
+        return dense_index.search_candidates(q, rows, rows_off, k, method=method, ascending=True)
+    return dense_index.search_candidates(q, rows, rows_off, k, method=method, ascending=True,
+                                         group_off=group_off)
 
 
 @torch.no_grad()
@@ -212,17 +217,20 @@ def predict_hybrid(args, k=100):
     index = ShardedDenseIndex(encode_corpus(model, texts, args.device),
                               dtype=getattr(args, "index_dtype", "bf16"))  # main.py --index-dtype
     method = getattr(args, "rerank_method", "auto")  # main.py --rerank-method
+    # main.py --rerank-unit: "page" ranks each claim's k best pages, each by its best line
+    # (row_off is the page -> row range map), so recall@k is over k pages
+    by_page = getattr(args, "rerank_unit", "line") == "page"
     hits = total = 0
     for batch in tqdm(loader, desc="Iteration"):
         claims = [d["claim"] for d in batch]
         s = time.time()
-        _, idx, _ = hybrid_search(model, index, sparse_index, row_off, claims, k, args.device,
-                                  method=method)
+        idx = hybrid_search(model, index, sparse_index, row_off, claims, k, args.device,
+                            method=method, group_off=row_off if by_page else None)[1]
         torch.cuda.synchronize()
         print(f"batch of {len(claims)} claims: {time.time() - s:.4f}s")
         for d, row in zip(batch, idx.cpu().tolist()):
             gold = {e["title"] for e in d["evidences"]}
             hits += int(any(titles[j] in gold for j in row if j >= 0))
             total += 1
-    print(f"evidence recall@{k}: {hits / max(total, 1):.4f}")
+    print(f"evidence recall@{k}{' (pages)' if by_page else ''}: {hits / max(total, 1):.4f}")
     return hits / max(total, 1)

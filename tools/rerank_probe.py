@@ -6,6 +6,8 @@ cross.
     python tools/rerank_probe.py --tables profiles/rerank_stream_probe.json  # + stream table
     python tools/rerank_probe.py --dtype fp8 > profiles/rerank_fp8_probe.json  # e4m3 shard
     python tools/rerank_probe.py --tables profiles/rerank_fp8_probe.json  # + fp8 / bf16 table
+    python tools/rerank_probe.py --grouped [--dtype fp8]   # top-k per group, see below
+    python tools/rerank_probe.py --tables profiles/rerank_group_probe.json
 
 One MI355X, the C3 shard (250k x 768 bf16, larger than the Infinity Cache), random
 ascending candidate lists of 0.1 / 1 / 5 / 25 % of the shard per query, Q in {1, 16, 64,
@@ -26,6 +28,10 @@ and the bf16 gathered and streamed calls of the same cells and list draws join t
 alternation window by window (``bf16_rerank_call_us``, ``bf16_stream_call_us``), so every
 fp8 time stands beside the bf16 time of the same run.  The crossovers of that file are the
 constants of retrieval.rerank_method(dtype="fp8").
+``--grouped``: the same cells and list draws, the grouped call (rerank_topk(group_off=...),
+pages of a fixed-seed draw, mean about 10 rows) alternating with the ungrouped call, gathered
+and streamed; profiles/rerank_group_probe.json holds the bf16 and the fp8 run's lines under
+"bf16" and "fp8".
 Prints a table to stderr and ONE JSON line to stdout."""
 import argparse
 import ctypes
@@ -160,8 +166,131 @@ def tables(path):
           f"{max(c['select_kernel_us'] for c in longest):.1f} us")
 
 
+def grouped_tables(r):
+    """The table of DESIGN.md 6e "Top-k per group": per cell and method the ungrouped call,
+    the grouped call on the same lists, their ratio, and the collapse span's own time."""
+    print(f"{r['dtype']}: {r['n_groups']:,} groups over {r['N']:,} rows "
+          f"(mean {r['N'] / r['n_groups']:.1f}, longest {r['max_group_rows']}), k = {r['k']}\n")
+    print("| Q | candidates / query | gather call | gather grouped | ratio | stream call | "
+          "stream grouped | ratio | collapse span |\n|---|---|---|---|---|---|---|---|---|")
+    for c in r["cells"]:
+        print(f"| {c['Q']} | {c['cand_per_query']:,} ({100 * c['frac']:g}%) | "
+              f"{c['gather_call_us']:,.1f} | {c['gather_grouped_call_us']:,.1f} | "
+              f"{c['gather_ratio']:.3f} | {c['stream_call_us']:,.1f} | "
+              f"{c['stream_grouped_call_us']:,.1f} | {c['stream_ratio']:.3f} | "
+              f"{c['collapse_span_us']:,.1f} |")
+    print()
+    worst = max(r["cells"], key=lambda c: max(c["spread_pct"].values()))
+    print(f"largest min-max spread of a cell's windows: {max(worst['spread_pct'].values()):.2f}% "
+          f"(Q = {worst['Q']}, {100 * worst['frac']:g}%); rounds per cell: {r['rounds']}")
+
+
+def grouped_probe(args):
+    """--grouped: the grouped call (group_off: pages of a fixed-seed draw, mean about 10
+    rows) next to the ungrouped call on the same lists, gathered and streamed, alternating
+    window by window; the collapse span (memset excluded: the two collapse phases) from a
+    profiled pass of its own.  ONE JSON line to stdout."""
+    from irc_amd import _lib, retrieval
+
+    fp8 = args.dtype == "fp8"
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(2025)
+    docs = torch.nn.functional.normalize(
+        torch.randn(args.n, args.d, generator=g)).bfloat16().to(dev)
+    torch.manual_seed(2025)
+    if fp8:
+        docs = retrieval.quantize_fp8(docs)
+    descale = 1.0 / (retrieval.FP8_SCALE * retrieval.FP8_SCALE)
+    # page sizes: 1 + an exponential draw of mean 9.5, rounded down -- mean about 10 rows
+    sizes = 1 + torch.empty(args.n, dtype=torch.float64).exponential_(1 / 9.5, generator=g).long()
+    ends = torch.cumsum(sizes, 0)
+    ends = ends[: int((ends < args.n).sum())]
+    group_off = torch.cat([torch.zeros(1, dtype=torch.int64), ends,
+                           torch.tensor([args.n])]).to(dev)
+    max_rows = int((group_off[1:] - group_off[:-1]).max())
+    cells = []
+    for Q in args.q:
+        qq = torch.nn.functional.normalize(
+            torch.randn(Q, args.d, generator=g)).bfloat16().to(dev)
+        if fp8:
+            qq = retrieval.quantize_fp8(qq)
+        for frac in args.frac:
+            n = max(1, int(round(frac * args.n)))
+            cands = [torch.cat([torch.randperm(args.n, device=dev)[:n].sort().values
+                                for _ in range(Q)]).to(torch.int32) for _ in range(args.sets)]
+            off = torch.arange(Q + 1, device=dev, dtype=torch.int64) * n
+
+            def make(method, go):
+                counter = [0]
+
+                def call():
+                    counter[0] += 1
+                    c = cands[counter[0] % args.sets]
+                    if fp8:
+                        return retrieval.rerank_topk_fp8(qq, docs, c, off, args.k, 0, descale,
+                                                         method=method, ascending=True,
+                                                         group_off=go)
+                    return retrieval.rerank_topk(qq, docs, c, off, args.k, method=method,
+                                                 ascending=True, group_off=go)
+                return call
+
+            timed = [(f"{m}{s}", make(m, go)) for m in ("gather", "stream")
+                     for s, go in (("", None), ("_grouped", group_off))]
+            est = {}
+            for name, fn in timed:
+                for _ in range(3):
+                    fn()
+                torch.cuda.synchronize()
+                est[name] = _window_ms(fn, 5)
+            reps = {m: max(2 * args.sets, min(4000, int(args.window_ms / max(est[m], 1e-3))))
+                    for m in est}
+            for m in reps:
+                reps[m] -= reps[m] % args.sets  # every draw equally often
+            t = {m: [] for m, _ in timed}
+            for _ in range(args.rounds):  # alternate them window by window
+                for m, fn in timed:
+                    t[m].append(_window_ms(fn, reps[m]))
+            lib.irc_prof_reset()
+            lib.irc_prof_enable(1)
+            for _ in range(min(reps["gather_grouped"], 12 * args.sets)):
+                timed[1][1]()
+            torch.cuda.synchronize()
+            lib.irc_prof_enable(0)
+            collapse_us, _ = _prof(lib, b"rerank_collapse")
+            med = {m: statistics.median(t[m]) * 1e3 for m in t}
+            cell = {"Q": Q, "frac": frac, "cand_per_query": n, "n_cand": Q * n,
+                    "collapse_span_us": collapse_us, "reps": reps,
+                    "spread_pct": {m: 100.0 * (max(t[m]) - min(t[m])) / statistics.median(t[m])
+                                   for m in t}}
+            for m in t:
+                cell[f"{m}_call_us"] = med[m]
+                cell[f"{m}_call_us_minmax"] = [min(t[m]) * 1e3, max(t[m]) * 1e3]
+            for m in ("gather", "stream"):
+                cell[f"{m}_ratio"] = med[f"{m}_grouped"] / med[m]
+            cells.append(cell)
+            print(f"Q={Q:4d} frac={frac:6.3f} n_cand={Q * n:9d}  gather {med['gather']:9.1f} / "
+                  f"grouped {med['gather_grouped']:9.1f} us ({cell['gather_ratio']:.3f})  stream "
+                  f"{med['stream']:9.1f} / grouped {med['stream_grouped']:9.1f} us "
+                  f"({cell['stream_ratio']:.3f})  collapse {collapse_us:7.1f} us",
+                  file=sys.stderr, flush=True)
+    print(json.dumps({"probe": "rerank_grouped", "device": torch.cuda.get_device_name(0),
+                      "dtype": args.dtype, "N": args.n, "D": args.d, "k": args.k,
+                      "rounds": args.rounds, "window_ms": args.window_ms, "sets": args.sets,
+                      "n_groups": int(group_off.numel() - 1), "max_group_rows": max_rows,
+                      "cells": cells}))
+
+
 def main():
     if len(sys.argv) == 3 and sys.argv[1] == "--tables":
+        with open(sys.argv[2]) as f:
+            rec = json.load(f)
+        if isinstance(rec, dict) and rec.get("probe") == "rerank_grouped":
+            return grouped_tables(rec)
+        if isinstance(rec, dict) and "bf16" in rec and "fp8" in rec:  # the two grouped runs
+            grouped_tables(rec["bf16"])
+            print()
+            return grouped_tables(rec["fp8"])
         return tables(sys.argv[2])
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=250_000)
@@ -175,10 +304,14 @@ def main():
     ap.add_argument("--frac", type=float, nargs="*", default=[0.001, 0.01, 0.05, 0.25])
     ap.add_argument("--dtype", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: the e4m3 calls, with the bf16 calls of the same cells alongside")
+    ap.add_argument("--grouped", action="store_true",
+                    help="time rerank_topk(group_off=...) next to the ungrouped call")
     args = ap.parse_args()
     fp8 = args.dtype == "fp8"
     if not torch.cuda.is_available():
         raise SystemExit("rerank_probe measures on a HIP device; none is visible")
+    if args.grouped:
+        return grouped_probe(args)
     from irc_amd import _lib, retrieval
 
     lib = _lib.load()
