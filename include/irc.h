@@ -323,6 +323,24 @@ int irc_gemm_set_big_dma(int on);
  * stride ldb, bf16) span less than 2^31 bytes, so that every byte offset of the
  * buffer-addressed staging fits 31 bits; else 0. */
 int irc_gemm_big_dma_fits(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb);
+/* L2 touch prefetch of that loop on its buffer-addressed tiles, row-major tile order only:
+ * the workgroups that one XCD runs together and that share an operand tile each read one
+ * dword of a disjoint part of its 128-byte lines, two K-tiles ahead, so that every sharer's
+ * LDS-DMA then hits the L2.  mode 0 = off, 1 = launches of at most two column tiles (the
+ * default, or what IRC_GEMM_L2_TOUCH set: where it measured a gain on MI355X), 2 = every
+ * launch that can take it.  The loaded values are unused: results are bit-identical.
+ * Returns the previous mode. */
+int irc_gemm_set_l2_touch(int mode);
+/* Host-only: the touches that the sharers of one operand tile (operand 0 = A, 1 = B;
+ * `lines` 128-byte lines per K-tile, at most 512) issue over nk K-tiles at a distance of
+ * dist K-tiles, for a launch of tiles_m x tiles_n tiles with `window` tiles resident per
+ * XCD, computed by the kernel's own assignment.  count / owner: [nk][lines] int32, the
+ * number of touches of each line and the rank that issued the last (-1: none); *sharers
+ * (optional): the number of ranks.  Returns the number of touches outside the tile's
+ * lines or past K (0 for a sound assignment), -1 on bad arguments. */
+int64_t irc_gemm_l2_touch_map(int operand, int64_t tiles_m, int64_t tiles_n, int64_t window,
+                              int64_t lines, int64_t nk, int64_t dist, int32_t* count,
+                              int32_t* owner, int32_t* sharers);
 
 /* The ping-pong 256 x 256 bf16 GEMM path: 1 = on (the default, or what IRC_GEMM_PP set),
  * 0 = off, so every bf16 launch goes to the big-tile or the general kernel (tests and A/B

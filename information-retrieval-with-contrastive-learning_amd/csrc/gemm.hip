@@ -74,6 +74,7 @@ struct Args {
   int group_m;       // big-tile kernel: grouped tile order (irc_common.h); 0 = row-major
   LnArgs ln;         // LayerNorm fold (big-tile kernel, bf16 C, vectorised epilogue)
   int big_dma;       // big-tile 16x16x32 loop: buffer-addressed staging allowed (launch_big)
+  int l2_touch;      // that loop's L2 touch prefetch: tiles resident on an XCD, 0 = off
 };
 
 // bf16 K-outer (COL / KN) slabs are kept k-major in LDS: [BK=32 k][128 rows]
@@ -490,6 +491,75 @@ inline bool dma_fits(int64_t rows, int64_t K, int64_t ld) {
   return ((rows - 1) * ld + K) * 2 < (1ll << 31);
 }
 
+// L2 touch prefetch of mainloop_mf16.  The workgroups an XCD runs at one time
+// (`window` consecutive tiles of its row-major band, one per CU) ask for the same operand
+// lines at the same moment: the tiles_n column tiles of a row tile share its A rows, the row
+// tiles of the window share B's column tiles.  Each line is fetched once per XCD, but every
+// sharer's LDS-DMA waits out the miss in its own queue.  So each of an operand's S sharers
+// reads one dword of a disjoint 1/S of the 128-byte lines of K-tile kt + TOUCH_D (line r =
+// the K-tile's 128 bytes of tile row r) while K-tile kt + 1 is staged, and the later DMA of
+// every sharer finds them in the L2.
+//   A: S_a = min(tiles_n, window), rank tn mod S_a.
+//   B: S_b = min(max(1, window / tiles_n), tiles_m), rank tm mod S_b (any S_b consecutive
+//      row tiles, wherever the window starts, carry the ranks 0 .. S_b - 1).
+// Rank p owns lines [p lines / S, (p + 1) lines / S); thread t of the workgroup touches its
+// tile's owned line t (at most 384 lines, 512 threads).  The sharing is a guess about what
+// runs together: a wrong one wastes or misses touches and changes no result.
+#ifndef IRC_BIG_TOUCH_D
+#define IRC_BIG_TOUCH_D 2
+#endif
+constexpr int TOUCH_D = IRC_BIG_TOUCH_D;  // K-tiles ahead (2: 6d-3 has 1 and 3)
+struct Touch {
+  int a_lo, a_n, b_lo, b_n;  // first owned line and their number, per operand (n = 0: none)
+};
+__host__ __device__ inline void touch_share(int tiles_m, int tiles_n, int window, int tm, int tn,
+                                            int& s_a, int& rank_a, int& s_b, int& rank_b) {
+  s_a = tiles_n < window ? tiles_n : window;
+  s_a = s_a < 1 ? 1 : s_a;
+  rank_a = tn % s_a;
+  s_b = window / (tiles_n < 1 ? 1 : tiles_n);
+  s_b = s_b > tiles_m ? tiles_m : s_b;
+  s_b = s_b < 1 ? 1 : s_b;
+  rank_b = tm % s_b;
+}
+__host__ __device__ inline void touch_range(int lines, int s, int rank, int& lo, int& n) {
+  lo = rank * lines / s;
+  n = (rank + 1) * lines / s - lo;
+}
+// window = 0 (off): no line.
+__host__ __device__ inline Touch touch_lines(int window, int tiles_m, int tiles_n, int tm, int tn,
+                                             int a_lines, int b_lines) {
+  Touch t{0, 0, 0, 0};
+  if (window <= 0) return t;
+  int s_a, rank_a, s_b, rank_b;
+  touch_share(tiles_m, tiles_n, window, tm, tn, s_a, rank_a, s_b, rank_b);
+  touch_range(a_lines, s_a, rank_a, t.a_lo, t.a_n);
+  touch_range(b_lines, s_b, rank_b, t.b_lo, t.b_n);
+  return t;
+}
+// One dword per lane of `mask` from base + voff + soff into a register nothing reads.  The
+// compiler does not count this load, so `sink` stays live ("+v" here, and once more after
+// the loop's last vmcnt(0)) and its register is not reused while a touch is in flight.  A
+// dword outside the descriptor's num_records bytes is not fetched.  The K loop runs with
+// every lane of its 512-thread workgroup active (uniform control flow), which is the exec
+// mask restored here.
+__device__ __forceinline__ void touch_dword(uint32_t& sink, __amdgpu_buffer_rsrc_t rsrc,
+                                            uint32_t voff, uint32_t soff, uint64_t mask) {
+#ifdef __HIP_DEVICE_COMPILE__
+  asm volatile(
+      "s_mov_b64 exec, %1\n\t"
+      "buffer_load_dword %0, %2, %3, %4 offen\n\t"
+      "s_mov_b64 exec, -1"
+      : "+v"(sink)
+      : "s"(mask), "v"(voff), "s"(rsrc), "s"(soff));
+#endif
+}
+__device__ __forceinline__ void touch_done(uint32_t sink) {
+#ifdef __HIP_DEVICE_COMPILE__
+  asm volatile("" ::"v"(sink));
+#endif
+}
+
 // Ring form (RING = true): 32-deep K-tiles in 4 LDS slots (64-byte rows, 40 KB a
 // slot at 256 x 384), three in flight: K-tile kt + 3 is issued into the slot K-tile
 // kt - 1 used, right after the one barrier of iteration kt (every wave is past its
@@ -551,7 +621,7 @@ __device__ __forceinline__ void mainloop_mf16(const unsigned short* A, int64_t l
                                               const unsigned short* B, int64_t ldb, int m0,
                                               int n0, int M, int N, int K, char* lds, int wave,
                                               int lane, f32x4 (&acc4)[8][2 * WNB], bool dma,
-                                              int ls = 0, int sh = 6) {
+                                              const Touch tch, int ls = 0, int sh = 6) {
   constexpr int BN = 128 * WNB;
   constexpr int A_BYTES = BM * ROW_BYTES, STAGE = A_BYTES + BN * ROW_BYTES;
   const int wm = wave >> 2, wn = wave & 3;
@@ -568,6 +638,22 @@ __device__ __forceinline__ void mainloop_mf16(const unsigned short* A, int64_t l
   const uint32_t a_tile = (uint32_t)a_row0 * (uint32_t)lda * 2u;
   const uint32_t b_tile = (uint32_t)n0 * (uint32_t)ldb * 2u;
   uint32_t a_lane = 0, b_lane = 0;
+  // The touch prefetch (touch_lines; buffer-addressed tiles only): the lane's owned line as a
+  // byte offset from the tile's first row, and the wave's owning lanes as an exec mask.  A
+  // slot-layout row r is token min(r mod 64, ls - 1) of the tile's sequence r / 64.
+  uint32_t ta_lane = 0, tb_lane = 0, sink = 0;
+  uint64_t ta_mask = 0, tb_mask = 0;
+  int touch_nk = 0;  // K-tiles kt < touch_nk issue touches (one uniform test when there are none)
+  if (buf && (tch.a_n | tch.b_n) != 0) {
+    touch_nk = nk - TOUCH_D;
+    const int t = wave * 64 + lane;
+    const int ar = tch.a_lo + t;
+    const int arow = ls == 0 ? ar : (ar >> 6) * ls + min(ar & 63, ls - 1);
+    ta_lane = (uint32_t)arow * (uint32_t)lda * 2u;
+    tb_lane = (uint32_t)(tch.b_lo + t) * (uint32_t)ldb * 2u;
+    ta_mask = __builtin_amdgcn_ballot_w64(t < tch.a_n);
+    tb_mask = __builtin_amdgcn_ballot_w64(t < tch.b_n);
+  }
   if (buf) {
     a_lane = dma_lane_off(lda, wave, lane, ls);
     b_lane = dma_lane_off(ldb, wave, lane);
@@ -594,6 +680,11 @@ __device__ __forceinline__ void mainloop_mf16(const unsigned short* A, int64_t l
       const uint32_t kb = (uint32_t)(kt + 1) * ROW_BYTES;
       stage_buf<BM>(ra, a_lane, a_tile + kb, a_pass, nxt, wave);
       stage_buf<BN>(rb, b_lane, b_tile + kb, b_pass, nxt + A_BYTES, wave);
+      if (kt < touch_nk) {  // the vmcnt(0) that ends this K-tile covers the touches
+        const uint32_t kd = (uint32_t)(kt + TOUCH_D) * ROW_BYTES;
+        if (ta_mask != 0) touch_dword(sink, ra, ta_lane, a_tile + kd, ta_mask);
+        if (tb_mask != 0) touch_dword(sink, rb, tb_lane, b_tile + kd, tb_mask);
+      }
     } else if (more) {
       // edge tiles and launches outside the gate: the 64-bit DMA addresses are re-derived
       // per K-tile (kept live through the loop they would push the 16x16 fragments into
@@ -628,6 +719,7 @@ __device__ __forceinline__ void mainloop_mf16(const unsigned short* A, int64_t l
     __syncthreads();
     BSTAMP(kt, 4);
   }
+  touch_done(sink);
 }
 }  // namespace big
 
@@ -660,6 +752,31 @@ inline std::atomic<int>& big_dma_mode() {
 inline int big_dma_flag(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb) {
   return big_dma_mode().load(std::memory_order_relaxed) != 0 && big::dma_fits(M, K, lda) &&
          big::dma_fits(N, K, ldb);
+}
+
+// The L2 touch prefetch of that loop (big::touch_lines), for buffer-addressed
+// launches in row-major tile order.  Mode 1 (the default) takes it where a launch has at most
+// two column tiles: there every A line has at most two readers, so A streams from HBM nearly
+// once per tile, and the out-proj / FFN2 kernel of the C2 step measured 105.4-106.1 ->
+// 103.0-103.1 us with it; FFN1 and the fused QKV (eight and six column tiles: most of their
+// A reads hit the L2 already) measured equal or 1-2% slower (profiles/l2touch_*).  Mode 2
+// takes it for every such launch (tests, A/B), 0 for none.  IRC_GEMM_L2_TOUCH (read once)
+// or irc_gemm_set_l2_touch set the mode.  The value passed to the kernel is the number of
+// tiles an XCD runs at one time (one per CU, eight XCDs), 0 = no touches.
+constexpr int L2_TOUCH_MAX_TILES_N = 2;
+inline std::atomic<int>& l2_touch_mode() {
+  static std::atomic<int> mode{[] {
+    const char* e = getenv("IRC_GEMM_L2_TOUCH");
+    return e && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : 1;
+  }()};
+  return mode;
+}
+inline int l2_touch_flag(int big_dma, int group_m, int64_t tiles_n) {
+  const int mode = l2_touch_mode().load(std::memory_order_relaxed);
+  if (mode == 0 || !big_dma || group_m > 1) return 0;
+  if (mode == 1 && tiles_n > L2_TOUCH_MAX_TILES_N) return 0;
+  const int cus = gpp::cu_count();
+  return cus >= 8 ? cus / 8 : 32;
 }
 
 // The staged epilogue of the default big-tile form (16x16x32 accumulators, bf16 C, 16-byte
@@ -933,7 +1050,8 @@ __global__ __launch_bounds__(big::NT, 1) void gemm_big_kernel(Args g) {
     __syncthreads();  // the epilogue's staging rows overlap the ring
   } else if constexpr (MF16) {
     big::mainloop_mf16<WNB>(A, g.lda, B, g.ldb, m0, n0, g.M, g.N, g.K, lds, wave, lane, acc4,
-                            g.big_dma != 0);
+                            g.big_dma != 0,
+                            big::touch_lines(g.l2_touch, tiles_m, tiles_n, tm, tn, BM, BN));
   } else {
   const int nk = g.K / BK;
   big::stage<BM>(A, g.lda, m0, g.M, 0, lds, wave, lane);
@@ -1263,6 +1381,7 @@ struct QaArgs {
   int L;                    // sequence length, 1..128
   int group_m;              // grouped tile order (grouped_tile; 0 = row-major)
   int big_dma;              // buffer-addressed staging allowed (see gemm::Args)
+  int l2_touch;             // L2 touch prefetch: tiles resident on an XCD, 0 = off (gemm::Args)
 };
 
 //
@@ -1310,7 +1429,8 @@ __global__ __launch_bounds__(big::NT, 1) void qkv_attn_kernel(QaArgs g) {
 #pragma unroll
     for (int j = 0; j < 2 * WNB; ++j) acc4[i][j] = (f32x4)0.0f;
   big::mainloop_mf16<WNB>(g.x, g.ldx, g.w, g.K, m0, n0, g.M, 3 * g.H, g.K, lds, wave, lane, acc4,
-                          g.big_dma != 0, ls, SH);
+                          g.big_dma != 0,
+                          big::touch_lines(g.l2_touch, tiles_m, tiles_n, tm, tn, BM, BN), ls, SH);
 
   unsigned short* T = reinterpret_cast<unsigned short*>(lds);    // [128][TP] staged half
   float* mbw = reinterpret_cast<float*>(lds + 128 * TP * 2) + SL * wave;  // this wave's key bias
@@ -1615,6 +1735,7 @@ static int launch_big(const Args& g0, int batch, int wnb, hipStream_t st) {
   Args g = g0;
   g.big_dma = big_dma_flag(g.M, g.N, g.K, g.lda, g.ldb);
   const int bn = 128 * wnb;
+  g.l2_touch = l2_touch_flag(g.big_dma, g.group_m, (g.N + bn - 1) / bn);
   const int tiles = ((g.M + big::BM - 1) / big::BM) * ((g.N + bn - 1) / bn);
   prof_begin(st);
   const bool ring = big_ring() && g.K % big::BK4 == 0;
@@ -1835,7 +1956,8 @@ extern "C" int irc_qkv_attention(int64_t M, int64_t H, int64_t heads, int64_t L,
   IRC_REQUIRE(bias_perm != nullptr, "qkv_attention: bias required");
   QaArgs a{static_cast<const unsigned short*>(x), static_cast<const unsigned short*>(wqkv_perm),
            bias_perm, mask, static_cast<unsigned short*>(ctx), (int)M, (int)H, (int)H, ldx, ldc,
-           0.125f, (int)L, IRC_GEMM_GROUP_M, big_dma_flag(M, 3 * H, H, ldx, H)};
+           0.125f, (int)L, IRC_GEMM_GROUP_M, big_dma_flag(M, 3 * H, H, ldx, H), 0};
+  a.l2_touch = l2_touch_flag(a.big_dma, a.group_m, 3 * H / 384);
   // Row-major tile order here even where Wqkv exceeds an XCD's 4 MB L2 (C4: 6 MB): grouped
   // (8 rows) measured 11.35-11.39k against 11.38-11.43k pairs/s on the C4 leg, GEMM traffic
   // 407 vs 415 MB per launch (profiles/r06_n/)
@@ -1892,6 +2014,56 @@ extern "C" int irc_gemm_set_big_dma(int on) {
 // ldb, bf16) passes the gate of the buffer-addressed staging.
 extern "C" int irc_gemm_big_dma_fits(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb) {
   return irc::gemm::big::dma_fits(M, K, lda) && irc::gemm::big::dma_fits(N, K, ldb) ? 1 : 0;
+}
+
+// The L2 touch prefetch of the big-tile kernel's 16x16x32 loop and of qkv_attn_kernel: 0 off,
+// 1 launches of at most two column tiles (the default), 2 every launch that can take it;
+// returns the previous mode.
+extern "C" int irc_gemm_set_l2_touch(int mode) {
+  return irc::gemm::l2_touch_mode().exchange(mode < 0 ? 0 : mode > 2 ? 2 : mode);
+}
+
+// Host-only: the touches of one operand (0 = A, 1 = B, `lines` lines per K-tile) that the
+// sharers of one line set issue over a K loop of nk K-tiles, by the kernel's own arithmetic
+// (big::touch_lines, thread t of a rank touching its owned line t of K-tile kt + dist while
+// kt + dist < nk).  count[k * lines + r] receives the number of touches of line r of K-tile
+// k and owner[...] the rank of the last one (-1: none); *sharers the number of ranks.
+// Returns the number of touches that fell outside the tile's lines or past K (0 when the
+// assignment is sound), or -1 on bad arguments.
+extern "C" int64_t irc_gemm_l2_touch_map(int operand, int64_t tiles_m, int64_t tiles_n,
+                                         int64_t window, int64_t lines, int64_t nk,
+                                         int64_t dist, int32_t* count, int32_t* owner,
+                                         int32_t* sharers) {
+  using namespace irc::gemm;
+  if ((operand != 0 && operand != 1) || tiles_m < 1 || tiles_n < 1 || window < 1 || lines < 1 ||
+      lines > big::NT || nk < 1 || dist < 1 || tiles_m > (1 << 20) || tiles_n > (1 << 20) ||
+      window > (1 << 20) || !count || !owner)
+    return -1;
+  for (int64_t i = 0; i < nk * lines; ++i) count[i] = 0, owner[i] = -1;
+  int s_a, rank_a, s_b, rank_b;
+  big::touch_share((int)tiles_m, (int)tiles_n, (int)window, 0, 0, s_a, rank_a, s_b, rank_b);
+  const int s = operand == 0 ? s_a : s_b;
+  if (sharers) *sharers = s;
+  int64_t outside = 0;
+  for (int rank = 0; rank < s; ++rank) {
+    // a tile of that rank: column tile `rank` (A), row tile `rank` (B)
+    const big::Touch t = big::touch_lines((int)window, (int)tiles_m, (int)tiles_n,
+                                          operand == 0 ? 0 : rank, operand == 0 ? rank : 0,
+                                          (int)lines, (int)lines);
+    const int lo = operand == 0 ? t.a_lo : t.b_lo, n = operand == 0 ? t.a_n : t.b_n;
+    for (int64_t kt = 0; kt + dist < nk; ++kt)
+      for (int th = 0; th < big::NT; ++th) {
+        if (th >= n) continue;  // the exec mask
+        const int64_t k = kt + dist, r = lo + th;
+        if (r < 0 || r >= lines || k >= nk) {
+          ++outside;
+          continue;
+        }
+        ++count[k * lines + r];
+        owner[k * lines + r] = rank;
+      }
+  }
+  return outside;
 }
 
 // 4-slot ring (1) or 2-slot loop (0, the default: the ring measured no faster on

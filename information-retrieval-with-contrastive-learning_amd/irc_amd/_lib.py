@@ -78,6 +78,8 @@ SIGNATURES = {
     "irc_gemm_set_big_mf16": (I32, [I32]),
     "irc_gemm_set_big_dma": (I32, [I32]),
     "irc_gemm_big_dma_fits": (I32, [I64, I64, I64, I64, I64]),
+    "irc_gemm_set_l2_touch": (I32, [I32]),
+    "irc_gemm_l2_touch_map": (I64, [I32, I64, I64, I64, I64, I64, I64, P, P, P]),
     "irc_gemm_set_pp": (I32, [I32]),
     "irc_scan_set_ppl_min_q": (I32, [I32]),
     "irc_embed_ln": (I32, [I32, P, P, P, P, P, P, P, I64, I64, I64, F32, P]),

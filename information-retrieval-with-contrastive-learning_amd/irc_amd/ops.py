@@ -109,6 +109,31 @@ def gemm_big_dma_fits(M, N, K, lda, ldb) -> bool:
     return bool(_lib.load().irc_gemm_big_dma_fits(M, N, K, lda, ldb))
 
 
+def gemm_set_l2_touch(mode) -> int:
+    """L2 touch prefetch of the big-tile bf16 GEMM's 16x16x32 loop and of qkv_attention
+    (irc_gemm_set_l2_touch): 0 / False off, 1 / True launches of at most two column tiles (the
+    default: where it measured a gain on MI355X), 2 every launch that can take
+    it.  Bit-identical results.  Returns the previous mode."""
+    return int(_lib.load().irc_gemm_set_l2_touch(int(mode)))
+
+
+def gemm_l2_touch_map(operand, tiles_m, tiles_n, window, lines, nk, dist):
+    """irc_gemm_l2_touch_map (host only, numpy): (count, owner, sharers, outside) -- per
+    (K-tile, line) the touches the sharers of one operand tile issue and the rank of the
+    last, the number of ranks, and the number of touches outside the tile or past K."""
+    import numpy as np
+
+    count = np.empty((nk, lines), dtype=np.int32)
+    owner = np.empty((nk, lines), dtype=np.int32)
+    sharers = ctypes.c_int(0)
+    outside = _lib.load().irc_gemm_l2_touch_map(
+        int(operand), tiles_m, tiles_n, window, lines, nk, dist, count.ctypes.data,
+        owner.ctypes.data, ctypes.addressof(sharers))
+    if outside < 0:
+        raise ValueError("gemm_l2_touch_map: bad arguments")
+    return count, owner, int(sharers.value), int(outside)
+
+
 def gemm_set_pp(on) -> int:
     """The ping-pong 256x256 bf16 GEMM path (irc_gemm_set_pp): True = on (the default),
     False = every bf16 launch goes to the big-tile or the general kernel.  Returns the
