@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
+
 #include "irc.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -63,6 +65,22 @@ void prof_end(const char* name, hipStream_t st, double work = 0.0);
 void prof_work(const char* name, double work);
 
 static inline hipStream_t as_stream(irc_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// ---- host-side argument rules shared by the scan and the candidate top-k ----
+
+// the embedding widths the dense kernels are instantiated for
+static inline bool supported_d(int64_t D) {
+  return D == 64 || D == 128 || D == 256 || D == 384 || D == 512 || D == 768 || D == 1024;
+}
+
+// score_scale of the e4m3 entries: a finite positive power of two (the multiply is exact)
+static inline bool pow2_scale(float s) {
+  int e;
+  return s > 0.f && std::isfinite(s) && std::frexp(s, &e) == 0.5f;
+}
+
+// workspace regions start on 256-byte boundaries
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ---- device helpers ----
 

@@ -39,6 +39,14 @@
 //  * irc_rerank_topk_grouped ranks groups of rows (pages) instead of rows: after any of the
 //    four scoring passes rerank_collapse_kernel zeroes every key that is not the maximum of
 //    its (query, group) run, and the unchanged select returns the top-k distinct groups.
+//
+// Layout: each thing exists once.  Device: score_chunk<E4M3, D> is the scoring body of both
+// gathered kernels (Operand<E4M3, D> holds what differs: piece type, pieces per lane, row
+// bytes, the dot product of a piece); chunk_owners is the owner search of the scoring and
+// the collapse kernels.  Host: the five extern "C" entries are one call of rerank_run each,
+// which holds the argument checks (their order is part of the interface), then runs
+// score_gather (the D switch) or score_stream (the pick GEMM's arguments), the collapse if
+// grouped, and the select.  A new operand type is one more Operand; a new entry one more Form.
 #include <stdint.h>
 
 #include <cmath>
@@ -59,16 +67,6 @@ constexpr int S_NH = 4;        // histogram copies (waves w, w + 4, ... share on
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// acc += <a, b> over the 8 bf16 pairs of one 16-byte piece, element order 0..7
-__device__ __forceinline__ float dot8(u32x4 a, u32x4 b, float acc) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    acc = fmaf(__uint_as_float(a[j] << 16), __uint_as_float(b[j] << 16), acc);
-    acc = fmaf(__uint_as_float(a[j] & 0xffff0000u), __uint_as_float(b[j] & 0xffff0000u), acc);
-  }
-  return acc;
-}
-
 // number of q in [lo, hi) with cand_off[q + 1] <= i, plus lo: the owner of flat
 // candidate i when it lies in [lo, hi]
 __device__ __forceinline__ int owner_of(const int64_t* __restrict__ cand_off, int lo, int hi,
@@ -81,84 +79,26 @@ __device__ __forceinline__ int owner_of(const int64_t* __restrict__ cand_off, in
   return lo;
 }
 
-template <int D>
-__global__ __launch_bounds__(RR_CHUNK) void rerank_score_kernel(
-    const unsigned short* __restrict__ queries, const unsigned short* __restrict__ docs, int Q,
-    int64_t N, const int32_t* __restrict__ cand, const int64_t* __restrict__ cand_off,
-    int64_t n_cand, int64_t doc_offset, uint64_t* __restrict__ keys) {
-  constexpr int NC = D / 64;  // 16-byte pieces per lane per row
-  const int tid = threadIdx.x;
-  const int sub = tid & (RR_LPR - 1);
-  const int64_t i0 = (int64_t)blockIdx.x * RR_CHUNK;
-  const int64_t i = i0 + tid;
-  const int64_t ilast = (i0 + RR_CHUNK <= n_cand ? i0 + RR_CHUNK : n_cand) - 1;
-
-  // the chunk's first and last owner (two independent searches, one latency), then this
-  // thread's own within that range: nothing left to search inside one long list
-  int qa, qb;
-  {
-    int lo_a = 0, hi_a = Q, lo_b = 0, hi_b = Q;
-    while (lo_a < hi_a || lo_b < hi_b) {
-      if (lo_a < hi_a) {
-        const int mid = (lo_a + hi_a) >> 1;
-        if (cand_off[mid + 1] <= i0) lo_a = mid + 1;
-        else hi_a = mid;
-      }
-      if (lo_b < hi_b) {
-        const int mid = (lo_b + hi_b) >> 1;
-        if (cand_off[mid + 1] <= ilast) lo_b = mid + 1;
-        else hi_b = mid;
-      }
+// The owners qa, qb of a chunk's first and last flat candidate i0, ilast: owner_of twice over
+// [0, Q), as two independent searches in one loop (one latency, not two).  A thread's own
+// owner then lies in [qa, qb]: nothing left to search inside one long list.
+__device__ __forceinline__ void chunk_owners(const int64_t* __restrict__ cand_off, int Q,
+                                             int64_t i0, int64_t ilast, int& qa, int& qb) {
+  int lo_a = 0, hi_a = Q, lo_b = 0, hi_b = Q;
+  while (lo_a < hi_a || lo_b < hi_b) {
+    if (lo_a < hi_a) {
+      const int mid = (lo_a + hi_a) >> 1;
+      if (cand_off[mid + 1] <= i0) lo_a = mid + 1;
+      else hi_a = mid;
     }
-    qa = lo_a;
-    qb = lo_b;
-  }
-  int myq = 0;
-  int myrow = -1;  // row in this shard, -1: not scored (past the end / another shard)
-  uint32_t gid = 0;
-  if (i < n_cand) {
-    myq = owner_of(cand_off, qa, qb, i);
-    myq = myq < Q - 1 ? myq : Q - 1;  // cand_off[Q] < n_cand (caller's error): stay in bounds
-    const int64_t id = (int64_t)cand[i];
-    const int64_t r = id - doc_offset;
-    if (r >= 0 && r < N) {
-      myrow = (int)r;
-      gid = (uint32_t)id;
+    if (lo_b < hi_b) {
+      const int mid = (lo_b + hi_b) >> 1;
+      if (cand_off[mid + 1] <= ilast) lo_b = mid + 1;
+      else hi_b = mid;
     }
   }
-
-  // group g = tid / 8 scores candidates 8 g .. 8 g + 7 one after the other, its 8 lanes
-  // sharing each row; lane s keeps the score of candidate 8 g + s
-  u32x4 qv[NC];
-  int qcur = -1;
-  float myscore = 0.f;
-#pragma unroll 1
-  for (int r = 0; r < RR_LPR; ++r) {
-    const int row = __shfl(myrow, r, RR_LPR);
-    const int qq = __shfl(myq, r, RR_LPR);
-    float acc = 0.f;
-    if (row >= 0) {  // uniform over the 8-lane group
-      if (qq != qcur) {
-        const u32x4* qp =
-            reinterpret_cast<const u32x4*>(queries + (int64_t)qq * D) + sub;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) qv[c] = qp[c * RR_LPR];
-        qcur = qq;
-      }
-      const u32x4* dp = reinterpret_cast<const u32x4*>(docs + (int64_t)row * D) + sub;
-      u32x4 dv[NC];
-#pragma unroll
-      for (int c = 0; c < NC; ++c) dv[c] = dp[c * RR_LPR];
-#pragma unroll
-      for (int c = 0; c < NC; ++c) acc = dot8(qv[c], dv[c], acc);
-    }
-    // every lane takes part (the exchange stays inside the 8-lane group)
-    acc += __shfl_xor(acc, 1, 64);
-    acc += __shfl_xor(acc, 2, 64);
-    acc += __shfl_xor(acc, 4, 64);
-    if (sub == r) myscore = acc;
-  }
-  if (i < n_cand) keys[i] = myrow >= 0 ? make_key(myscore, gid) : 0ull;
+  qa = lo_a;
+  qb = lo_b;
 }
 
 // acc += <a, b> over the 4 e4m3 pairs of one 32-bit word, element order 0..3
@@ -175,46 +115,59 @@ __device__ __forceinline__ float dot4_e4m3(uint32_t a, uint32_t b, float acc) {
   return acc;
 }
 
-// rerank_score_kernel for e4m3 shards (irc_rerank_topk_fp8): rows of D bytes.  The same
-// walk, owner searches and 8-lane row sharing; lane s reads the 16-byte pieces s, s + 8,
-// ... (one 128-byte granule per step), and at D = 64, where a row is half a granule, the
-// 8-byte pieces s.  The query slice stays in registers as codes.  One summation order per
-// (query, doc): each lane's pieces ascending in one fmaf chain, then xor-shuffles 1, 2, 4.
-// The key's score is the sum times score_scale (a power of two: exact).
+// What the scoring body needs to know of its operands.  A lane reads NC pieces of a row,
+// piece c at piece index s + 8 c: 16-byte pieces (8 lanes x 16 B = one 128-byte granule per
+// step), and 8-byte ones for e4m3 at D = 64, where a row is half a granule.  dot() adds a
+// piece's products to acc in ascending element order, one fmaf chain.
+template <bool E4M3, int D>
+struct Operand;
 template <int D>
-__global__ __launch_bounds__(RR_CHUNK) void rerank_score_fp8_kernel(
-    const unsigned char* __restrict__ queries, const unsigned char* __restrict__ docs, int Q,
-    int64_t N, const int32_t* __restrict__ cand, const int64_t* __restrict__ cand_off,
-    int64_t n_cand, int64_t doc_offset, float score_scale, uint64_t* __restrict__ keys) {
-  constexpr int PW = D >= 128 ? 4 : 2;          // 32-bit words per piece
-  constexpr int NC = D / (RR_LPR * PW * 4);     // pieces per lane per row
-  static_assert(NC * RR_LPR * PW * 4 == D, "a row is a whole number of 8-lane steps");
+struct Operand<false, D> {  // bf16
+  typedef u32x4 piece_t;
+  static constexpr int ROW_BYTES = D * 2;
+  static constexpr int NC = D / 64;
+  static __device__ __forceinline__ float dot(piece_t a, piece_t b, float acc) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      acc = fmaf(__uint_as_float(a[j] << 16), __uint_as_float(b[j] << 16), acc);
+      acc = fmaf(__uint_as_float(a[j] & 0xffff0000u), __uint_as_float(b[j] & 0xffff0000u), acc);
+    }
+    return acc;
+  }
+};
+template <int D>
+struct Operand<true, D> {  // e4m3 codes
+  static constexpr int PW = D >= 128 ? 4 : 2;  // 32-bit words per piece
   typedef uint32_t piece_t __attribute__((ext_vector_type(PW)));
+  static constexpr int ROW_BYTES = D;
+  static constexpr int NC = D / (RR_LPR * PW * 4);
+  static __device__ __forceinline__ float dot(piece_t a, piece_t b, float acc) {
+#pragma unroll
+    for (int w = 0; w < PW; ++w) acc = dot4_e4m3(a[w], b[w], acc);
+    return acc;
+  }
+};
+
+// The scoring body of both gathered kernels: keys[i] of flat candidate i, one workgroup per
+// chunk of RR_CHUNK.  score_scale (a power of two: exact) applies to e4m3 only.
+template <bool E4M3, int D>
+__device__ __forceinline__ void score_chunk(
+    const char* __restrict__ queries, const char* __restrict__ docs, int Q, int64_t N,
+    const int32_t* __restrict__ cand, const int64_t* __restrict__ cand_off, int64_t n_cand,
+    int64_t doc_offset, float score_scale, uint64_t* __restrict__ keys) {
+  typedef Operand<E4M3, D> Op;
+  typedef typename Op::piece_t piece_t;
+  constexpr int NC = Op::NC;  // pieces per lane per row
+  static_assert(NC * RR_LPR * (int)sizeof(piece_t) == Op::ROW_BYTES,
+                "a row is a whole number of 8-lane steps");
   const int tid = threadIdx.x;
   const int sub = tid & (RR_LPR - 1);
   const int64_t i0 = (int64_t)blockIdx.x * RR_CHUNK;
   const int64_t i = i0 + tid;
   const int64_t ilast = (i0 + RR_CHUNK <= n_cand ? i0 + RR_CHUNK : n_cand) - 1;
 
-  // the chunk's first and last owner, then this thread's own (rerank_score_kernel)
   int qa, qb;
-  {
-    int lo_a = 0, hi_a = Q, lo_b = 0, hi_b = Q;
-    while (lo_a < hi_a || lo_b < hi_b) {
-      if (lo_a < hi_a) {
-        const int mid = (lo_a + hi_a) >> 1;
-        if (cand_off[mid + 1] <= i0) lo_a = mid + 1;
-        else hi_a = mid;
-      }
-      if (lo_b < hi_b) {
-        const int mid = (lo_b + hi_b) >> 1;
-        if (cand_off[mid + 1] <= ilast) lo_b = mid + 1;
-        else hi_b = mid;
-      }
-    }
-    qa = lo_a;
-    qb = lo_b;
-  }
+  chunk_owners(cand_off, Q, i0, ilast, qa, qb);
   int myq = 0;
   int myrow = -1;  // row in this shard, -1: not scored (past the end / another shard)
   uint32_t gid = 0;
@@ -229,6 +182,8 @@ __global__ __launch_bounds__(RR_CHUNK) void rerank_score_fp8_kernel(
     }
   }
 
+  // group g = tid / 8 scores candidates 8 g .. 8 g + 7 one after the other, its 8 lanes
+  // sharing each row; lane s keeps the score of candidate 8 g + s
   piece_t qv[NC];
   int qcur = -1;
   float myscore = 0.f;
@@ -239,19 +194,19 @@ __global__ __launch_bounds__(RR_CHUNK) void rerank_score_fp8_kernel(
     float acc = 0.f;
     if (row >= 0) {  // uniform over the 8-lane group
       if (qq != qcur) {
-        const piece_t* qp = reinterpret_cast<const piece_t*>(queries + (int64_t)qq * D) + sub;
+        const piece_t* qp =
+            reinterpret_cast<const piece_t*>(queries + (int64_t)qq * Op::ROW_BYTES) + sub;
 #pragma unroll
         for (int c = 0; c < NC; ++c) qv[c] = qp[c * RR_LPR];
         qcur = qq;
       }
-      const piece_t* dp = reinterpret_cast<const piece_t*>(docs + (int64_t)row * D) + sub;
+      const piece_t* dp =
+          reinterpret_cast<const piece_t*>(docs + (int64_t)row * Op::ROW_BYTES) + sub;
       piece_t dv[NC];
 #pragma unroll
       for (int c = 0; c < NC; ++c) dv[c] = dp[c * RR_LPR];
 #pragma unroll
-      for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int w = 0; w < PW; ++w) acc = dot4_e4m3(qv[c][w], dv[c][w], acc);
+      for (int c = 0; c < NC; ++c) acc = Op::dot(qv[c], dv[c], acc);
     }
     // every lane takes part (the exchange stays inside the 8-lane group)
     acc += __shfl_xor(acc, 1, 64);
@@ -259,7 +214,29 @@ __global__ __launch_bounds__(RR_CHUNK) void rerank_score_fp8_kernel(
     acc += __shfl_xor(acc, 4, 64);
     if (sub == r) myscore = acc;
   }
-  if (i < n_cand) keys[i] = myrow >= 0 ? make_key(myscore * score_scale, gid) : 0ull;
+  if constexpr (E4M3) myscore *= score_scale;
+  if (i < n_cand) keys[i] = myrow >= 0 ? make_key(myscore, gid) : 0ull;
+}
+
+template <int D>
+__global__ __launch_bounds__(RR_CHUNK) void rerank_score_kernel(
+    const unsigned short* __restrict__ queries, const unsigned short* __restrict__ docs, int Q,
+    int64_t N, const int32_t* __restrict__ cand, const int64_t* __restrict__ cand_off,
+    int64_t n_cand, int64_t doc_offset, uint64_t* __restrict__ keys) {
+  score_chunk<false, D>(reinterpret_cast<const char*>(queries),
+                        reinterpret_cast<const char*>(docs), Q, N, cand, cand_off, n_cand,
+                        doc_offset, 1.f, keys);
+}
+
+// rerank_score_kernel for e4m3 shards (irc_rerank_topk_fp8): rows of D bytes
+template <int D>
+__global__ __launch_bounds__(RR_CHUNK) void rerank_score_fp8_kernel(
+    const unsigned char* __restrict__ queries, const unsigned char* __restrict__ docs, int Q,
+    int64_t N, const int32_t* __restrict__ cand, const int64_t* __restrict__ cand_off,
+    int64_t n_cand, int64_t doc_offset, float score_scale, uint64_t* __restrict__ keys) {
+  score_chunk<true, D>(reinterpret_cast<const char*>(queries),
+                       reinterpret_cast<const char*>(docs), Q, N, cand, cand_off, n_cand,
+                       doc_offset, score_scale, keys);
 }
 
 __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
@@ -633,25 +610,9 @@ __global__ __launch_bounds__(RR_CHUNK) void rerank_collapse_kernel(
       s_samp[tid] = group_off[at < n_groups ? at : n_groups];
       if (tid == 0) s_first = group_off[0];
     }
-    // the chunk's first and last owner, then this thread's own (rerank_score_kernel)
+    // the chunk's first and last owner, then this thread's own (score_chunk)
     int qa, qb;
-    {
-      int lo_a = 0, hi_a = Q, lo_b = 0, hi_b = Q;
-      while (lo_a < hi_a || lo_b < hi_b) {
-        if (lo_a < hi_a) {
-          const int mid = (lo_a + hi_a) >> 1;
-          if (cand_off[mid + 1] <= i0) lo_a = mid + 1;
-          else hi_a = mid;
-        }
-        if (lo_b < hi_b) {
-          const int mid = (lo_b + hi_b) >> 1;
-          if (cand_off[mid + 1] <= ilast) lo_b = mid + 1;
-          else hi_b = mid;
-        }
-      }
-      qa = lo_a;
-      qb = lo_b;
-    }
+    chunk_owners(cand_off, Q, i0, ilast, qa, qb);
     int myq = -1, myg = -1;  // past the end: a run of its own, no key
     if (valid) {
       myq = owner_of(cand_off, qa, qb, i);
@@ -738,19 +699,23 @@ __global__ __launch_bounds__(RR_CHUNK) void rerank_collapse_kernel(
   }
 }
 
-static bool supported_d(int64_t D) {  // the scan's set (scan_topk.hip)
-  return D == 64 || D == 128 || D == 256 || D == 384 || D == 512 || D == 768 || D == 1024;
+// keys, and for the grouped form rmax and head after them: 8 bytes per candidate each, every
+// region on a 256-byte boundary
+static size_t region_bytes(int64_t n_cand) {
+  return align256((size_t)(n_cand > 0 ? n_cand : 0) * 8);
+}
+static size_t workspace_bytes_for(int64_t n_cand, bool grouped) {
+  return (grouped ? 3 : 1) * region_bytes(n_cand) + 256;
 }
 
-static bool pow2_scale(float s) {  // irc_scan_topk_fp8's rule (scan_topk.hip)
-  int e;
-  return s > 0.f && std::isfinite(s) && std::frexp(s, &e) == 0.5f;
-}
-
-static size_t workspace_bytes_for(int64_t n_cand) {
-  const size_t keys = (size_t)(n_cand > 0 ? n_cand : 0) * 8;
-  return ((keys + 255) & ~(size_t)255) + 256;
-}
+// What one of the extern "C" entries asks of rerank_run.
+struct Form {
+  const char* name;          // the prefix of its messages
+  bool stream, e4m3;         // the scoring pass: gathered / streamed, bf16 / e4m3 operands
+  bool grouped;              // top-k per group: the collapse between scoring and select
+  const int64_t* group_off;  // grouped only (null is the caller's error)
+  int64_t n_groups;
+};
 
 }  // namespace rerank
 }  // namespace irc
@@ -763,15 +728,152 @@ extern "C" int irc_rerank_chunk(void) { return RR_CHUNK; }
 extern "C" int64_t irc_rerank_topk_workspace(int64_t Q, int64_t n_cand, int64_t k) {
   (void)Q;
   (void)k;
-  return (int64_t)workspace_bytes_for(n_cand);
+  return (int64_t)workspace_bytes_for(n_cand, false);
+}
+
+extern "C" int64_t irc_rerank_topk_grouped_workspace(int64_t Q, int64_t n_cand, int64_t k) {
+  (void)Q;
+  (void)k;
+  return (int64_t)workspace_bytes_for(n_cand, true);
 }
 
 extern "C" int irc_rerank_stream_tile(void) { return gpp::PICK_TILE; }
 
-// The two scoring methods share the select launch.
-static int launch_select(const uint64_t* keys, const int64_t* cand_off, int64_t Q, int64_t n_cand,
-                         int64_t k, float* out_score, int64_t* out_idx, int32_t* out_n,
-                         hipStream_t st) {
+// The gathered scoring pass: keys[0 .. n_cand) from the candidates' rows.
+static int score_gather(const Form& f, const void* queries, const void* docs, int64_t Q,
+                        int64_t N, int64_t D, const int32_t* cand, const int64_t* cand_off,
+                        int64_t n_cand, int64_t doc_offset, float score_scale, uint64_t* keys,
+                        hipStream_t st) {
+  const unsigned blocks = (unsigned)((n_cand + RR_CHUNK - 1) / RR_CHUNK);
+  const unsigned short* qp = static_cast<const unsigned short*>(queries);
+  const unsigned short* dp = static_cast<const unsigned short*>(docs);
+  const unsigned char* qp8 = static_cast<const unsigned char*>(queries);
+  const unsigned char* dp8 = static_cast<const unsigned char*>(docs);
+  prof_begin(st);
+#define IRC_RR_CASE(DD)                                                                         \
+  case DD:                                                                                      \
+    if (f.e4m3)                                                                                 \
+      hipLaunchKernelGGL((rerank_score_fp8_kernel<DD>), dim3(blocks), dim3(RR_CHUNK), 0, st,    \
+                         qp8, dp8, (int)Q, N, cand, cand_off, n_cand, doc_offset, score_scale,  \
+                         keys);                                                                 \
+    else                                                                                        \
+      hipLaunchKernelGGL((rerank_score_kernel<DD>), dim3(blocks), dim3(RR_CHUNK), 0, st, qp,    \
+                         dp, (int)Q, N, cand, cand_off, n_cand, doc_offset, keys);              \
+    break;
+  switch (D) {
+    IRC_RR_CASE(64)
+    IRC_RR_CASE(128)
+    IRC_RR_CASE(256)
+    IRC_RR_CASE(384)
+    IRC_RR_CASE(512)
+    IRC_RR_CASE(768)
+    default: IRC_RR_CASE(1024)
+  }
+#undef IRC_RR_CASE
+  // the gathered row bytes
+  prof_end(f.e4m3 ? "rerank_fp8_score" : "rerank_score", st,
+           (double)n_cand * D * (f.e4m3 ? 1.0 : 2.0));
+  return check_launch(f.e4m3 ? "rerank_score_fp8_kernel" : "rerank_score_kernel");
+}
+
+// The streamed scoring pass (lists ascending in global id): the keys of the ids outside the
+// shard are zeroed, the others picked out of the score tiles of the ping-pong GEMM loop.
+static int score_stream(const Form& f, const void* queries, const void* docs, int64_t Q,
+                        int64_t N, int64_t D, const int32_t* cand, const int64_t* cand_off,
+                        int64_t n_cand, int64_t doc_offset, float score_scale, uint64_t* keys,
+                        hipStream_t st) {
+  prof_begin(st);
+  hipLaunchKernelGGL(rerank_foreign_kernel, dim3((unsigned)Q, RF_Y), dim3(RF_NT), 0, st, cand,
+                     cand_off, n_cand, doc_offset, N, keys);
+  if (N > 0) {
+    gpp::PArgs a{};
+    a.A = static_cast<const unsigned short*>(queries);
+    a.B = static_cast<const unsigned short*>(docs);
+    a.M = (int)Q;
+    a.N = (int)N;
+    a.K = (int)(f.e4m3 ? D / 2 : D);  // 2-byte units
+    a.kchunk = a.K;
+    a.lda = a.K;
+    a.ldb = a.K;
+    a.keys = keys;
+    a.cand = cand;
+    a.cand_off = cand_off;
+    a.n_cand = n_cand;
+    a.doc_offset = doc_offset;
+    if (f.e4m3) a.score_scale = score_scale;
+    gpp::run_pick(a, st, f.e4m3);
+  }
+  // the bytes the pass streams: the shard once per query tile
+  prof_end(f.e4m3 ? "rerank_fp8_stream_score" : "rerank_stream_score", st,
+           (double)((Q + 255) / 256) * (double)N * D * (f.e4m3 ? 1.0 : 2.0));
+  return check_launch(f.e4m3 ? "rerank_fp8_stream_score" : "rerank_stream_score");
+}
+
+// Every entry: the one sequence of argument checks, one scoring pass, the collapse if
+// grouped, the select.  The order of the checks is part of the interface
+// (tests/test_rerank_validation_cpu.py): a call that breaks two reports the earlier one.
+static int rerank_run(const Form& f, const void* queries, const void* docs, int64_t Q, int64_t N,
+                      int64_t D, const int32_t* cand, const int64_t* cand_off, int64_t n_cand,
+                      int64_t k, int64_t doc_offset, float score_scale, void* workspace,
+                      int64_t workspace_bytes, float* out_score, int64_t* out_idx,
+                      int32_t* out_n, irc_stream_t stream) {
+  IRC_REQUIRE(Q >= 0 && N >= 0 && n_cand >= 0, "%s: negative size", f.name);
+  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "%s: k=%lld outside [1, %d]", f.name, (long long)k,
+              RR_MAXK);
+  IRC_REQUIRE(supported_d(D), "%s: unsupported D=%lld", f.name, (long long)D);
+  IRC_REQUIRE(!(f.e4m3 && f.stream) || D % 128 == 0,
+              "%s: unsupported D=%lld for the e4m3 stream method (D %% 128 == 0)", f.name,
+              (long long)D);
+  IRC_REQUIRE(!f.e4m3 || pow2_scale(score_scale), "%s: score_scale must be a power of two",
+              f.name);
+  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
+              "%s: global doc ids must fit int32 (doc_offset + N < 2^31)", f.name);
+  IRC_REQUIRE(Q < (1ll << 31) - 1, "%s: Q too large", f.name);
+  IRC_REQUIRE(n_cand < (1ll << 31) * RR_CHUNK, "%s: n_cand too large", f.name);
+  // one workgroup per (query tile, doc tile): the grid and the kernel's int tile count
+  IRC_REQUIRE(!f.stream || ((Q + 255) / 256) * ((N + 255) / 256) < (1ll << 31),
+              "%s: Q x N too large for the stream method", f.name);
+  const int64_t need = (int64_t)workspace_bytes_for(n_cand, f.grouped);
+  if (workspace == nullptr || workspace_bytes < need) {
+    set_error("%s: workspace %lld < required %lld bytes", f.name, (long long)workspace_bytes,
+              (long long)need);
+    return IRC_E_WORKSPACE;
+  }
+  if (Q == 0) return IRC_OK;
+  IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n, "%s: null pointer", f.name);
+  IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)), "%s: null candidates / docs", f.name);
+  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
+              "%s: queries and docs must be 16-byte aligned", f.name);
+  if (f.grouped) {
+    IRC_REQUIRE(f.group_off != nullptr, "%s: null group_off", f.name);
+    IRC_REQUIRE(f.n_groups >= 0 && f.n_groups < (1ll << 31) - 1,
+                "%s: n_groups=%lld outside [0, 2^31 - 1)", f.name, (long long)f.n_groups);
+  }
+  hipStream_t st = as_stream(stream);
+  uint64_t* keys = static_cast<uint64_t*>(workspace);
+  if (n_cand > 0) {
+    if (int rc = (f.stream ? score_stream : score_gather)(f, queries, docs, Q, N, D, cand,
+                                                          cand_off, n_cand, doc_offset,
+                                                          score_scale, keys, st))
+      return rc;
+  }
+  if (f.grouped && n_cand > 0) {
+    const size_t region = region_bytes(n_cand);
+    unsigned long long* rmax =
+        reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + region);
+    int64_t* head = reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + 2 * region);
+    const unsigned blocks = (unsigned)((n_cand + RR_CHUNK - 1) / RR_CHUNK);
+    if (hipMemsetAsync(rmax, 0, (size_t)n_cand * 8, st) != hipSuccess)
+      return check_launch("rerank_collapse memset");
+    prof_begin(st);
+    hipLaunchKernelGGL((rerank_collapse_kernel<0>), dim3(blocks), dim3(RR_CHUNK), 0, st, cand,
+                       cand_off, (int)Q, n_cand, f.group_off, (int)f.n_groups, keys, rmax, head);
+    hipLaunchKernelGGL((rerank_collapse_kernel<1>), dim3(blocks), dim3(RR_CHUNK), 0, st, cand,
+                       cand_off, (int)Q, n_cand, f.group_off, (int)f.n_groups, keys, rmax, head);
+    // per key: key + id read, head written, then key + head + slot read
+    prof_end("rerank_collapse", st, (double)n_cand * 44.0);
+    if (int rc = check_launch("rerank_collapse_kernel")) return rc;
+  }
   prof_begin(st);
   hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)Q), dim3(SNT), 0, st, keys, cand_off,
                      n_cand, (int)k, out_score, out_idx, out_n);
@@ -779,151 +881,14 @@ static int launch_select(const uint64_t* keys, const int64_t* cand_off, int64_t 
   return check_launch("rerank_select_kernel");
 }
 
-// The scoring passes, each filling keys[0 .. n_cand): the gathered rows (irc_rerank_topk),
-// the streamed shard (irc_rerank_topk_stream) and the two on e4m3 operands.
-static int score_gather(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,
-                        const int32_t* cand, const int64_t* cand_off, int64_t n_cand,
-                        int64_t doc_offset, uint64_t* keys, hipStream_t st) {
-  if (n_cand > 0) {
-    const unsigned blocks = (unsigned)((n_cand + RR_CHUNK - 1) / RR_CHUNK);
-    const unsigned short* qp = static_cast<const unsigned short*>(queries);
-    const unsigned short* dp = static_cast<const unsigned short*>(docs);
-    prof_begin(st);
-#define IRC_RR_CASE(DD)                                                                      \
-  case DD:                                                                                   \
-    hipLaunchKernelGGL((rerank_score_kernel<DD>), dim3(blocks), dim3(RR_CHUNK), 0, st, qp, dp, \
-                       (int)Q, N, cand, cand_off, n_cand, doc_offset, keys);                 \
-    break;
-    switch (D) {
-      IRC_RR_CASE(64)
-      IRC_RR_CASE(128)
-      IRC_RR_CASE(256)
-      IRC_RR_CASE(384)
-      IRC_RR_CASE(512)
-      IRC_RR_CASE(768)
-      default: IRC_RR_CASE(1024)
-    }
-#undef IRC_RR_CASE
-    prof_end("rerank_score", st, (double)n_cand * D * 2.0);  // the gathered row bytes
-    if (int rc = check_launch("rerank_score_kernel")) return rc;
-  }
-  return IRC_OK;
-}
-
-static int score_stream(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,
-                        const int32_t* cand, const int64_t* cand_off, int64_t n_cand,
-                        int64_t doc_offset, uint64_t* keys, hipStream_t st) {
-  if (n_cand > 0) {
-    prof_begin(st);
-    hipLaunchKernelGGL(rerank_foreign_kernel, dim3((unsigned)Q, RF_Y), dim3(RF_NT), 0, st, cand,
-                       cand_off, n_cand, doc_offset, N, keys);
-    if (N > 0) {
-      gpp::PArgs a{};
-      a.A = static_cast<const unsigned short*>(queries);
-      a.B = static_cast<const unsigned short*>(docs);
-      a.M = (int)Q;
-      a.N = (int)N;
-      a.K = (int)D;
-      a.kchunk = a.K;
-      a.lda = D;
-      a.ldb = D;
-      a.keys = keys;
-      a.cand = cand;
-      a.cand_off = cand_off;
-      a.n_cand = n_cand;
-      a.doc_offset = doc_offset;
-      gpp::run_pick(a, st);
-    }
-    // the bytes the pass streams: the shard once per query tile
-    prof_end("rerank_stream_score", st, (double)((Q + 255) / 256) * (double)N * D * 2.0);
-    if (int rc = check_launch("rerank_stream_score")) return rc;
-  }
-  return IRC_OK;
-}
-
-static int score_fp8(bool stream, const void* queries, const void* docs, int64_t Q, int64_t N,
-                     int64_t D, const int32_t* cand, const int64_t* cand_off, int64_t n_cand,
-                     int64_t doc_offset, float score_scale, uint64_t* keys, hipStream_t st) {
-  if (n_cand > 0 && !stream) {
-    const unsigned blocks = (unsigned)((n_cand + RR_CHUNK - 1) / RR_CHUNK);
-    const unsigned char* qp = static_cast<const unsigned char*>(queries);
-    const unsigned char* dp = static_cast<const unsigned char*>(docs);
-    prof_begin(st);
-#define IRC_RR_CASE(DD)                                                                       \
-  case DD:                                                                                    \
-    hipLaunchKernelGGL((rerank_score_fp8_kernel<DD>), dim3(blocks), dim3(RR_CHUNK), 0, st, qp, \
-                       dp, (int)Q, N, cand, cand_off, n_cand, doc_offset, score_scale, keys); \
-    break;
-    switch (D) {
-      IRC_RR_CASE(64)
-      IRC_RR_CASE(128)
-      IRC_RR_CASE(256)
-      IRC_RR_CASE(384)
-      IRC_RR_CASE(512)
-      IRC_RR_CASE(768)
-      default: IRC_RR_CASE(1024)
-    }
-#undef IRC_RR_CASE
-    prof_end("rerank_fp8_score", st, (double)n_cand * D);  // the gathered row bytes
-    if (int rc = check_launch("rerank_score_fp8_kernel")) return rc;
-  }
-  if (n_cand > 0 && stream) {
-    prof_begin(st);
-    hipLaunchKernelGGL(rerank_foreign_kernel, dim3((unsigned)Q, RF_Y), dim3(RF_NT), 0, st, cand,
-                       cand_off, n_cand, doc_offset, N, keys);
-    if (N > 0) {
-      gpp::PArgs a{};
-      a.A = static_cast<const unsigned short*>(queries);
-      a.B = static_cast<const unsigned short*>(docs);
-      a.M = (int)Q;
-      a.N = (int)N;
-      a.K = (int)(D / 2);  // 2-byte units
-      a.kchunk = a.K;
-      a.lda = a.K;
-      a.ldb = a.K;
-      a.keys = keys;
-      a.cand = cand;
-      a.cand_off = cand_off;
-      a.n_cand = n_cand;
-      a.doc_offset = doc_offset;
-      a.score_scale = score_scale;
-      gpp::run_pick(a, st, true);
-    }
-    // the bytes the pass streams: the shard once per query tile
-    prof_end("rerank_fp8_stream_score", st, (double)((Q + 255) / 256) * (double)N * D);
-    if (int rc = check_launch("rerank_fp8_stream_score")) return rc;
-  }
-  return IRC_OK;
-}
-
 extern "C" int irc_rerank_topk(const void* queries, const void* docs, int64_t Q, int64_t N,
                                int64_t D, const int32_t* cand, const int64_t* cand_off,
                                int64_t n_cand, int64_t k, int64_t doc_offset, void* workspace,
                                int64_t workspace_bytes, float* out_score, int64_t* out_idx,
                                int32_t* out_n, irc_stream_t stream) {
-  IRC_REQUIRE(Q >= 0 && N >= 0 && n_cand >= 0, "rerank_topk: negative size");
-  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "rerank_topk: k=%lld outside [1, %d]", (long long)k,
-              RR_MAXK);
-  IRC_REQUIRE(supported_d(D), "rerank_topk: unsupported D=%lld", (long long)D);
-  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
-              "rerank_topk: global doc ids must fit int32 (doc_offset + N < 2^31)");
-  IRC_REQUIRE(Q < (1ll << 31) - 1, "rerank_topk: Q too large");
-  IRC_REQUIRE(n_cand < (1ll << 31) * RR_CHUNK, "rerank_topk: n_cand too large");
-  if (workspace == nullptr || workspace_bytes < (int64_t)workspace_bytes_for(n_cand)) {
-    set_error("rerank_topk: workspace %lld < required %lld bytes", (long long)workspace_bytes,
-              (long long)workspace_bytes_for(n_cand));
-    return IRC_E_WORKSPACE;
-  }
-  if (Q == 0) return IRC_OK;
-  IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n, "rerank_topk: null pointer");
-  IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)), "rerank_topk: null candidates / docs");
-  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
-              "rerank_topk: queries and docs must be 16-byte aligned");
-  hipStream_t st = as_stream(stream);
-  uint64_t* keys = static_cast<uint64_t*>(workspace);
-  if (int rc = score_gather(queries, docs, Q, N, D, cand, cand_off, n_cand, doc_offset, keys, st))
-    return rc;
-  return launch_select(keys, cand_off, Q, n_cand, k, out_score, out_idx, out_n, st);
+  return rerank_run({"rerank_topk", false, false, false, nullptr, 0}, queries, docs, Q, N, D,
+                    cand, cand_off, n_cand, k, doc_offset, 1.f, workspace, workspace_bytes,
+                    out_score, out_idx, out_n, stream);
 }
 
 extern "C" int irc_rerank_topk_stream(const void* queries, const void* docs, int64_t Q,
@@ -932,74 +897,9 @@ extern "C" int irc_rerank_topk_stream(const void* queries, const void* docs, int
                                       int64_t doc_offset, void* workspace,
                                       int64_t workspace_bytes, float* out_score,
                                       int64_t* out_idx, int32_t* out_n, irc_stream_t stream) {
-  // irc_rerank_topk's checks, in its order
-  IRC_REQUIRE(Q >= 0 && N >= 0 && n_cand >= 0, "rerank_topk: negative size");
-  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "rerank_topk: k=%lld outside [1, %d]", (long long)k,
-              RR_MAXK);
-  IRC_REQUIRE(supported_d(D), "rerank_topk: unsupported D=%lld", (long long)D);
-  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
-              "rerank_topk: global doc ids must fit int32 (doc_offset + N < 2^31)");
-  IRC_REQUIRE(Q < (1ll << 31) - 1, "rerank_topk: Q too large");
-  IRC_REQUIRE(n_cand < (1ll << 31) * RR_CHUNK, "rerank_topk: n_cand too large");
-  // one workgroup per (query tile, doc tile): the grid and the kernel's int tile count
-  IRC_REQUIRE(((Q + 255) / 256) * ((N + 255) / 256) < (1ll << 31),
-              "rerank_topk: Q x N too large for the stream method");
-  if (workspace == nullptr || workspace_bytes < (int64_t)workspace_bytes_for(n_cand)) {
-    set_error("rerank_topk: workspace %lld < required %lld bytes", (long long)workspace_bytes,
-              (long long)workspace_bytes_for(n_cand));
-    return IRC_E_WORKSPACE;
-  }
-  if (Q == 0) return IRC_OK;
-  IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n, "rerank_topk: null pointer");
-  IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)), "rerank_topk: null candidates / docs");
-  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
-              "rerank_topk: queries and docs must be 16-byte aligned");
-  hipStream_t st = as_stream(stream);
-  uint64_t* keys = static_cast<uint64_t*>(workspace);
-  if (int rc = score_stream(queries, docs, Q, N, D, cand, cand_off, n_cand, doc_offset, keys, st))
-    return rc;
-  return launch_select(keys, cand_off, Q, n_cand, k, out_score, out_idx, out_n, st);
-}
-
-// The two e4m3 entries: irc_rerank_topk's checks in its order, the e4m3 ones after the D
-// check, then one of the two scoring passes and the shared select.
-static int rerank_fp8_impl(bool stream, const void* queries, const void* docs, int64_t Q,
-                           int64_t N, int64_t D, const int32_t* cand, const int64_t* cand_off,
-                           int64_t n_cand, int64_t k, int64_t doc_offset, float score_scale,
-                           void* workspace, int64_t workspace_bytes, float* out_score,
-                           int64_t* out_idx, int32_t* out_n, irc_stream_t stream_) {
-  IRC_REQUIRE(Q >= 0 && N >= 0 && n_cand >= 0, "rerank_topk_fp8: negative size");
-  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "rerank_topk_fp8: k=%lld outside [1, %d]", (long long)k,
-              RR_MAXK);
-  IRC_REQUIRE(supported_d(D), "rerank_topk_fp8: unsupported D=%lld", (long long)D);
-  IRC_REQUIRE(!stream || D % 128 == 0,
-              "rerank_topk_fp8: unsupported D=%lld for the stream method (D %% 128 == 0)",
-              (long long)D);
-  IRC_REQUIRE(pow2_scale(score_scale), "rerank_topk_fp8: score_scale must be a power of two");
-  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
-              "rerank_topk_fp8: global doc ids must fit int32 (doc_offset + N < 2^31)");
-  IRC_REQUIRE(Q < (1ll << 31) - 1, "rerank_topk_fp8: Q too large");
-  IRC_REQUIRE(n_cand < (1ll << 31) * RR_CHUNK, "rerank_topk_fp8: n_cand too large");
-  IRC_REQUIRE(!stream || ((Q + 255) / 256) * ((N + 255) / 256) < (1ll << 31),
-              "rerank_topk_fp8: Q x N too large for the stream method");
-  if (workspace == nullptr || workspace_bytes < (int64_t)workspace_bytes_for(n_cand)) {
-    set_error("rerank_topk_fp8: workspace %lld < required %lld bytes", (long long)workspace_bytes,
-              (long long)workspace_bytes_for(n_cand));
-    return IRC_E_WORKSPACE;
-  }
-  if (Q == 0) return IRC_OK;
-  IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n,
-              "rerank_topk_fp8: null pointer");
-  IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)),
-              "rerank_topk_fp8: null candidates / docs");
-  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
-              "rerank_topk_fp8: queries and docs must be 16-byte aligned");
-  hipStream_t st = as_stream(stream_);
-  uint64_t* keys = static_cast<uint64_t*>(workspace);
-  if (int rc = score_fp8(stream, queries, docs, Q, N, D, cand, cand_off, n_cand, doc_offset,
-                         score_scale, keys, st))
-    return rc;
-  return launch_select(keys, cand_off, Q, n_cand, k, out_score, out_idx, out_n, st);
+  return rerank_run({"rerank_topk", true, false, false, nullptr, 0}, queries, docs, Q, N, D,
+                    cand, cand_off, n_cand, k, doc_offset, 1.f, workspace, workspace_bytes,
+                    out_score, out_idx, out_n, stream);
 }
 
 extern "C" int irc_rerank_topk_fp8(const void* queries, const void* docs, int64_t Q, int64_t N,
@@ -1008,9 +908,9 @@ extern "C" int irc_rerank_topk_fp8(const void* queries, const void* docs, int64_
                                    float score_scale, void* workspace, int64_t workspace_bytes,
                                    float* out_score, int64_t* out_idx, int32_t* out_n,
                                    irc_stream_t stream) {
-  return rerank_fp8_impl(false, queries, docs, Q, N, D, cand, cand_off, n_cand, k, doc_offset,
-                         score_scale, workspace, workspace_bytes, out_score, out_idx, out_n,
-                         stream);
+  return rerank_run({"rerank_topk_fp8", false, true, false, nullptr, 0}, queries, docs, Q, N, D,
+                    cand, cand_off, n_cand, k, doc_offset, score_scale, workspace,
+                    workspace_bytes, out_score, out_idx, out_n, stream);
 }
 
 extern "C" int irc_rerank_topk_stream_fp8(const void* queries, const void* docs, int64_t Q,
@@ -1020,25 +920,12 @@ extern "C" int irc_rerank_topk_stream_fp8(const void* queries, const void* docs,
                                           int64_t workspace_bytes, float* out_score,
                                           int64_t* out_idx, int32_t* out_n,
                                           irc_stream_t stream) {
-  return rerank_fp8_impl(true, queries, docs, Q, N, D, cand, cand_off, n_cand, k, doc_offset,
-                         score_scale, workspace, workspace_bytes, out_score, out_idx, out_n,
-                         stream);
+  return rerank_run({"rerank_topk_fp8", true, true, false, nullptr, 0}, queries, docs, Q, N, D,
+                    cand, cand_off, n_cand, k, doc_offset, score_scale, workspace,
+                    workspace_bytes, out_score, out_idx, out_n, stream);
 }
 
-// keys | rmax | head, each region aligned as irc_rerank_topk's one
-static size_t grouped_region_bytes(int64_t n_cand) {
-  return (((size_t)(n_cand > 0 ? n_cand : 0) * 8) + 255) & ~(size_t)255;
-}
-
-extern "C" int64_t irc_rerank_topk_grouped_workspace(int64_t Q, int64_t n_cand, int64_t k) {
-  (void)Q;
-  (void)k;
-  return (int64_t)(3 * grouped_region_bytes(n_cand) + 256);
-}
-
-// The top-k per group: irc_rerank_topk's checks in its order (the stream and e4m3 ones where
-// those entries have them), the group checks last; one of the four scoring passes, the two
-// collapse phases, the shared select.
+// The top-k per group, over any of the four scoring passes (flags).
 extern "C" int irc_rerank_topk_grouped(const void* queries, const void* docs, int64_t Q,
                                        int64_t N, int64_t D, const int32_t* cand,
                                        const int64_t* cand_off, int64_t n_cand, int64_t k,
@@ -1046,66 +933,9 @@ extern "C" int irc_rerank_topk_grouped(const void* queries, const void* docs, in
                                        int64_t n_groups, uint32_t flags, float score_scale,
                                        void* workspace, int64_t workspace_bytes,
                                        float* out_score, int64_t* out_idx, int32_t* out_n,
-                                       irc_stream_t stream_) {
-  const bool stream = (flags & IRC_RERANK_STREAM) != 0, e4m3 = (flags & IRC_RERANK_E4M3) != 0;
-  IRC_REQUIRE(Q >= 0 && N >= 0 && n_cand >= 0, "rerank_topk_grouped: negative size");
-  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "rerank_topk_grouped: k=%lld outside [1, %d]",
-              (long long)k, RR_MAXK);
-  IRC_REQUIRE(supported_d(D), "rerank_topk_grouped: unsupported D=%lld", (long long)D);
-  IRC_REQUIRE(!(e4m3 && stream) || D % 128 == 0,
-              "rerank_topk_grouped: unsupported D=%lld for the e4m3 stream method "
-              "(D %% 128 == 0)", (long long)D);
-  IRC_REQUIRE(!e4m3 || pow2_scale(score_scale),
-              "rerank_topk_grouped: score_scale must be a power of two");
-  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
-              "rerank_topk_grouped: global doc ids must fit int32 (doc_offset + N < 2^31)");
-  IRC_REQUIRE(Q < (1ll << 31) - 1, "rerank_topk_grouped: Q too large");
-  IRC_REQUIRE(n_cand < (1ll << 31) * RR_CHUNK, "rerank_topk_grouped: n_cand too large");
-  IRC_REQUIRE(!stream || ((Q + 255) / 256) * ((N + 255) / 256) < (1ll << 31),
-              "rerank_topk_grouped: Q x N too large for the stream method");
-  const int64_t need = irc_rerank_topk_grouped_workspace(Q, n_cand, k);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("rerank_topk_grouped: workspace %lld < required %lld bytes",
-              (long long)workspace_bytes, (long long)need);
-    return IRC_E_WORKSPACE;
-  }
-  if (Q == 0) return IRC_OK;
-  IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n,
-              "rerank_topk_grouped: null pointer");
-  IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)),
-              "rerank_topk_grouped: null candidates / docs");
-  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
-              "rerank_topk_grouped: queries and docs must be 16-byte aligned");
-  IRC_REQUIRE(group_off != nullptr, "rerank_topk_grouped: null group_off");
-  IRC_REQUIRE(n_groups >= 0 && n_groups < (1ll << 31) - 1,
-              "rerank_topk_grouped: n_groups=%lld outside [0, 2^31 - 1)", (long long)n_groups);
-  hipStream_t st = as_stream(stream_);
-  const size_t region = grouped_region_bytes(n_cand);
-  uint64_t* keys = static_cast<uint64_t*>(workspace);
-  unsigned long long* rmax =
-      reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + region);
-  int64_t* head = reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + 2 * region);
-  int rc;
-  if (e4m3)
-    rc = score_fp8(stream, queries, docs, Q, N, D, cand, cand_off, n_cand, doc_offset,
-                   score_scale, keys, st);
-  else if (stream)
-    rc = score_stream(queries, docs, Q, N, D, cand, cand_off, n_cand, doc_offset, keys, st);
-  else
-    rc = score_gather(queries, docs, Q, N, D, cand, cand_off, n_cand, doc_offset, keys, st);
-  if (rc) return rc;
-  if (n_cand > 0) {
-    const unsigned blocks = (unsigned)((n_cand + RR_CHUNK - 1) / RR_CHUNK);
-    if (hipMemsetAsync(rmax, 0, (size_t)n_cand * 8, st) != hipSuccess)
-      return check_launch("rerank_collapse memset");
-    prof_begin(st);
-    hipLaunchKernelGGL((rerank_collapse_kernel<0>), dim3(blocks), dim3(RR_CHUNK), 0, st, cand,
-                       cand_off, (int)Q, n_cand, group_off, (int)n_groups, keys, rmax, head);
-    hipLaunchKernelGGL((rerank_collapse_kernel<1>), dim3(blocks), dim3(RR_CHUNK), 0, st, cand,
-                       cand_off, (int)Q, n_cand, group_off, (int)n_groups, keys, rmax, head);
-    // per key: key + id read, head written, then key + head + slot read
-    prof_end("rerank_collapse", st, (double)n_cand * 44.0);
-    if (int rc2 = check_launch("rerank_collapse_kernel")) return rc2;
-  }
-  return launch_select(keys, cand_off, Q, n_cand, k, out_score, out_idx, out_n, st);
+                                       irc_stream_t stream) {
+  return rerank_run({"rerank_topk_grouped", (flags & IRC_RERANK_STREAM) != 0,
+                     (flags & IRC_RERANK_E4M3) != 0, true, group_off, n_groups},
+                    queries, docs, Q, N, D, cand, cand_off, n_cand, k, doc_offset, score_scale,
+                    workspace, workspace_bytes, out_score, out_idx, out_n, stream);
 }

@@ -2091,10 +2091,6 @@ static void launch_dense(int eb, int64_t D, int ks, int Q, const DenseArgs& a, h
   else launch_dense_eb<2>(D, ks, Q, a, st);
 }
 
-static bool supported_d(int64_t D) {
-  return D == 64 || D == 128 || D == 256 || D == 384 || D == 512 || D == 768 || D == 1024;
-}
-
 static void launch_select(const RegionSource& src, int Q, int k, int mode, uint64_t* thr,
                           float* out_score, int64_t* out_idx, float smul, hipStream_t st);
 
@@ -2116,8 +2112,6 @@ static int64_t chunk_docs(int64_t Q, int64_t N, int64_t D, int64_t k, int eb) {
   const int64_t nch = (ntiles + tiles - 1) / tiles;
   return (ntiles + nch - 1) / nch * 256;  // balanced chunks of whole 256-doc tiles
 }
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Workspace of a chunked scan: the per-chunk lists [nch][Q][k] (fp32 scores, int64 ids)
 // ahead of one chunk's own plan.
@@ -2424,11 +2418,6 @@ extern "C" int irc_scan_topk_many(const void* const* queries, int64_t batches, c
   }
   for (int s = 0; s <= nd; ++s) hipEventDestroy(ev[s]);
   return rc;
-}
-
-static bool pow2_scale(float s) {
-  int e;
-  return s > 0.f && std::isfinite(s) && std::frexp(s, &e) == 0.5f;
 }
 
 extern "C" int irc_scan_topk_fp8(const void* queries, const void* docs, int64_t Q, int64_t N,

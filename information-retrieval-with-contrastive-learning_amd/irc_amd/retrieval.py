@@ -324,21 +324,30 @@ def rerank_topk(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
     d = contig(docs, torch.bfloat16)
     if d.shape[1] != q.shape[1]:
         raise ValueError(f"dim mismatch: queries D={q.shape[1]}, docs D={d.shape[1]}")
-    entry = "irc_rerank_topk_stream" if method == "stream" else "irc_rerank_topk"
-    return _rerank_call(entry, (), q, d, cand, cand_off, k, doc_offset, ws_tag, method, ascending,
+    return _rerank_call(q, d, cand, cand_off, k, doc_offset, 1.0, ws_tag, method, ascending,
                         group_off)
 
 
-def _rerank_call(entry, extra, q, d, cand, cand_off, k, doc_offset, ws_tag, method, ascending,
+# (method, e4m3 operands) -> the ungrouped native entry and the grouped entry's flags word
+_RERANK_FORMS = {
+    ("gather", False): ("irc_rerank_topk", 0),
+    ("stream", False): ("irc_rerank_topk_stream", RERANK_FLAG_STREAM),
+    ("gather", True): ("irc_rerank_topk_fp8", RERANK_FLAG_E4M3),
+    ("stream", True): ("irc_rerank_topk_stream_fp8", RERANK_FLAG_STREAM | RERANK_FLAG_E4M3),
+}
+
+
+def _rerank_call(q, d, cand, cand_off, k, doc_offset, score_scale, ws_tag, method, ascending,
                  group_off=None):
     """The part of ``rerank_topk`` and ``rerank_topk_fp8`` after their operand checks: the
-    id handling, the sort under "stream", the outputs and the native call (``extra``: the
-    entry's arguments between doc_offset and the workspace).  With ``group_off`` the one
-    grouped entry takes the place of ``entry``: the scoring form goes in its flags word,
-    ``extra`` (the e4m3 entries' score_scale) in its score_scale."""
+    id handling, the sort under "stream", the outputs and the native call.  The operands'
+    dtype (uint8: e4m3 codes) and ``method`` choose the entry, or with ``group_off`` the
+    flags word of the one grouped entry; ``score_scale`` counts for e4m3 operands only."""
     Q, D = q.shape
     N = d.shape[0]
     grouped = group_off is not None
+    e4m3 = q.dtype == torch.uint8
+    entry, flags = _RERANK_FORMS[method, e4m3]
     ordered = grouped or method == "stream"  # the kernels need ascending lists
     if cand.dtype not in (torch.int32, torch.int64):
         raise TypeError(f"cand must be int32 or int64, not {cand.dtype}")
@@ -358,18 +367,15 @@ def _rerank_call(entry, extra, q, d, cand, cand_off, k, doc_offset, ws_tag, meth
     out_s = torch.empty((Q, k), dtype=torch.float32, device=q.device)
     out_i = torch.empty((Q, k), dtype=torch.int64, device=q.device)
     out_n = torch.empty((Q,), dtype=torch.int32, device=q.device)
-    if not grouped:
+    if not grouped:  # 8 bytes of workspace per candidate, against 24 for the grouped entry
         nbytes = int(_lib.fn("irc_rerank_topk_workspace")(Q, n_cand, k))
         ws = workspace(nbytes, q.device, ws_tag)
         _lib.call(entry, ptr(q), ptr(d), Q, N, D, ptr(c), ptr(off), n_cand, k,
-                  doc_offset, *extra, ptr(ws), ws.numel(), ptr(out_s), ptr(out_i), ptr(out_n),
-                  stream_ptr(q.device))
+                  doc_offset, *((score_scale,) if e4m3 else ()), ptr(ws), ws.numel(),
+                  ptr(out_s), ptr(out_i), ptr(out_n), stream_ptr(q.device))
         return out_s, out_i, out_n
     go = group_off.contiguous()
     n_groups = go.numel() - 1
-    flags = (RERANK_FLAG_STREAM if method == "stream" else 0) | \
-        (RERANK_FLAG_E4M3 if q.dtype == torch.uint8 else 0)
-    score_scale = float(extra[0]) if extra else 1.0
     nbytes = int(_lib.fn("irc_rerank_topk_grouped_workspace")(Q, n_cand, k))
     ws = workspace(nbytes, q.device, ws_tag)
     _lib.call("irc_rerank_topk_grouped", ptr(q), ptr(d), Q, N, D, ptr(c), ptr(off), n_cand, k,
@@ -397,9 +403,8 @@ def rerank_topk_fp8(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tenso
     _require_e4m3(queries, docs)  # a wrong dtype is a TypeError on any device
     q, d = _fp8_operands(queries, docs)
     require_hip(cand, cand_off)
-    entry = "irc_rerank_topk_stream_fp8" if method == "stream" else "irc_rerank_topk_fp8"
-    return _rerank_call(entry, (float(score_scale),), q, d, cand, cand_off, k, doc_offset, ws_tag,
-                        method, ascending, group_off)
+    return _rerank_call(q, d, cand, cand_off, k, doc_offset, float(score_scale), ws_tag, method,
+                        ascending, group_off)
 
 
 def expand_ranges(cand: torch.Tensor, cand_off: torch.Tensor, row_off: torch.Tensor):

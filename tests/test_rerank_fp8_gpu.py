@@ -49,7 +49,10 @@ def _same(a, b):
 
 
 GATHER_CASES = [(1, 1, 128, 1, 0), (3, 40, 128, 8, 11), (33, 4099, 64, 10, 0),
-                (257, 4099, 128, 100, 5), (16, 20000, 768, 1024, 3), (7, 9000, 1024, 1, 0)]
+                (257, 4099, 128, 100, 5), (16, 20000, 768, 1024, 3), (7, 9000, 1024, 1, 0),
+                # the other widths of the one scoring body; Q = 5 starts the cycle at C - 1:
+                # 1368 candidates, chunks that span several owners
+                (5, 300, 256, 8, 0), (5, 300, 384, 8, 7), (5, 300, 512, 8, 0)]
 # (5, 200, 128): one partial doc tile; (257, 4099, 384): three K-tiles, a second query tile
 # of one row, a last doc tile of 3 docs
 STREAM_CASES = [c for c in GATHER_CASES if c[2] != 64] + [(5, 200, 128, 8, 0),

@@ -65,7 +65,10 @@ def _lengths(k, N):
 
 
 GRID_CASES = [(1, 1, 64, 1, 0), (3, 40, 128, 8, 11), (33, 4099, 64, 10, 0),
-              (257, 4099, 128, 100, 5), (16, 20000, 768, 1024, 3), (7, 9000, 1024, 1, 0)]
+              (257, 4099, 128, 100, 5), (16, 20000, 768, 1024, 3), (7, 9000, 1024, 1, 0),
+              # the other widths of the one scoring body; Q = 10 is the whole cycle of
+              # lengths, 1393 candidates: chunks that span several owners
+              (10, 300, 256, 8, 0), (10, 300, 384, 8, 7), (10, 300, 512, 8, 0)]
 
 
 def _grid_case(Q, N, D, k, doc_offset):
