@@ -193,6 +193,37 @@ int irc_rerank_topk_grouped(const void* queries, const void* docs, int64_t Q, in
                             float* out_score, int64_t* out_idx, int32_t* out_n,
                             irc_stream_t stream);
 
+/* Merge P per-shard GROUPED top-k lists: the reduce step of irc_rerank_topk_grouped over
+ * several shards, as irc_topk_merge is of the scan.  A group whose best rows lie in two
+ * shards is in two lists; irc_topk_merge would return it twice.
+ *
+ * in_score / in_idx [P, Q, kin]: global row ids, -1 (any negative id) an empty slot whose
+ * score is not read.  A list need not be sorted and its empty slots may lie anywhere.
+ * group_off [n_groups + 1] as for irc_rerank_topk_grouped; a row below group_off[0] or from
+ * group_off[n_groups] on is in no group and never eligible.  Per query every entry gets the
+ * ranking key of its (score, id); of the entries of one group only the largest key stays
+ * (equal scores keep the lower row id); the outputs are the kout largest of those by (score
+ * desc, id asc), irc_scan_topk's rule (NaN lowest, -0 = +0), slots past them (-inf, -1),
+ * out_n[q] = min(kout, distinct groups with an entry).  Exact and deterministic: the only
+ * atomics are maxima.  Merging the per-shard grouped top-k lists gives the grouped top-k of
+ * the whole corpus ("Across shards").
+ *
+ * Caller's contract: ids < 2^31 (a larger one counts as an empty slot) and no row id in two
+ * entries of one query (each row lives in one shard); a repeated id may be returned twice.
+ * Nothing is read or written out of bounds.
+ *
+ * Limits: P >= 1, Q >= 0, kin >= 1, 1 <= kout <= 1024, P * kin <= 8192 (8 shards x 1024),
+ * 0 <= n_groups < 2^31 - 1, then -- for Q > 0 -- group_off != NULL, a workspace of
+ * irc_topk_merge_grouped_workspace bytes (8 per entry and 8 per query) and no null array:
+ * each violation is IRC_E_INVALID with a message that starts "topk_merge_grouped:", found
+ * before any device work.  Q == 0 returns IRC_OK and touches nothing. */
+int64_t irc_topk_merge_grouped_workspace(int64_t P, int64_t Q, int64_t kin);
+int irc_topk_merge_grouped(const float* in_score, const int64_t* in_idx, int64_t P, int64_t Q,
+                           int64_t kin, int64_t kout, const int64_t* group_off,
+                           int64_t n_groups, void* workspace, int64_t workspace_bytes,
+                           float* out_score, int64_t* out_idx, int32_t* out_n,
+                           irc_stream_t stream);
+
 /* Raw score tile for tests / diagnostics: out[Q, N] fp32 = queries . docs^T
  * using the same MFMA path as irc_scan_topk. */
 int irc_scan_scores(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,

@@ -39,6 +39,11 @@
 //  * irc_rerank_topk_grouped ranks groups of rows (pages) instead of rows: after any of the
 //    four scoring passes rerank_collapse_kernel zeroes every key that is not the maximum of
 //    its (query, group) run, and the unchanged select returns the top-k distinct groups.
+//  * irc_topk_merge_grouped is the reduce step of that call over several shards: the
+//    per-shard lists of a query hold one page twice when its best lines lie in two shards,
+//    so merge_collapse_kernel sorts the query's P * kin entries by row id (a group is a run
+//    of the sorted ids), keeps the maximum key of every group, and the same select returns
+//    the top-k distinct groups.
 //
 // Layout: each thing exists once.  Device: score_chunk<E4M3, D> is the scoring body of both
 // gathered kernels (Operand<E4M3, D> holds what differs: piece type, pieces per lane, row
@@ -699,6 +704,125 @@ __global__ __launch_bounds__(RR_CHUNK) void rerank_collapse_kernel(
   }
 }
 
+// Grouped merge (irc_topk_merge_grouped): the keys of the P lists of one query, at most
+// S_STAGE entries in all, with every key that is not the maximum of its group set to 0; the
+// unchanged select then runs over keys[q L .. (q + 1) L), L = P * kin.  One workgroup per
+// query, of one thread per pair of sort slots (64 to SNT threads), and everything in LDS:
+//  1. every entry becomes v = id << 32 | orderable score; an empty slot (id < 0; its score
+//     is not read), an id from 2^31 on and the padding up to a power of two are ~0;
+//  2. a bitonic sort makes v ascending.  The group is a non-decreasing function of the row
+//     id, so the entries of one group are one run of the sorted array, whatever list they
+//     came from, and the ~0 entries are its tail;
+//  3. every entry finds its group (group_of, from LDS samples) and the head of its run --
+//     the first sorted position whose id reaches the group's first row, a binary search in
+//     LDS -- and folds its key into s_rmax[head] with one 64-bit atomic max: the maximum
+//     does not depend on the order the atomics land in;
+//  4. the entry whose key equals its run's maximum keeps it, every other one writes 0.
+// Keys of one group are distinct while the row ids are (the caller's contract), so one
+// entry per group survives; a row id that appears twice may survive twice.  Every sorted
+// position below L writes its slot of keys[], so the workspace needs no clearing, and
+// workgroup q writes the select's offset q L (the last one also Q L).
+__global__ __launch_bounds__(SNT) void merge_collapse_kernel(
+    const float* __restrict__ in_score, const int64_t* __restrict__ in_idx, int P, int Q,
+    int kin, const int64_t* __restrict__ group_off, int n_groups, uint64_t* __restrict__ keys,
+    int64_t* __restrict__ list_off) {
+  __shared__ uint64_t s_v[S_STAGE];
+  __shared__ unsigned long long s_rmax[S_STAGE];
+  __shared__ int16_t s_head[S_STAGE];
+  __shared__ int64_t s_samp[RC_NS];
+  __shared__ int64_t s_first;
+  static_assert(S_STAGE <= 32768, "a run head fits int16");
+  const int q = blockIdx.x;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const int L = P * kin;  // <= S_STAGE
+  int npow = 1;
+  while (npow < L) npow <<= 1;
+  if (tid == 0) {
+    list_off[q] = (int64_t)q * L;
+    if (q == Q - 1) list_off[Q] = (int64_t)Q * L;
+  }
+  const int64_t stride = ((int64_t)n_groups + RC_NS - 1) / RC_NS;
+  if (n_groups > 0) {
+    for (int t = tid; t < RC_NS; t += nt) {
+      const int64_t at = (t + 1) * stride;
+      s_samp[t] = group_off[at < n_groups ? at : n_groups];
+    }
+    if (tid == 0) s_first = group_off[0];
+  }
+  for (int j = tid; j < npow; j += nt) {
+    uint64_t v = ~0ull;
+    if (j < L) {
+      const int p = j / kin;
+      const int64_t src = ((int64_t)p * Q + q) * kin + (j - p * kin);
+      const int64_t id = in_idx[src];
+      if (id >= 0 && id < (1ll << 31))
+        v = ((uint64_t)id << 32) | (uint64_t)orderable_f32(in_score[src]);
+    }
+    s_v[j] = v;
+    s_rmax[j] = 0ull;
+  }
+  __syncthreads();
+  for (int size = 2; size <= npow; size <<= 1) {
+    for (int st = size >> 1; st > 0; st >>= 1) {
+      for (int t = tid; t < (npow >> 1); t += nt) {
+        const int i = 2 * t - (t & (st - 1));
+        const int j = i + st;
+        const bool asc = (i & size) == 0;
+        const uint64_t a = s_v[i], b = s_v[j];
+        if ((a > b) == asc) {
+          s_v[i] = b;
+          s_v[j] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  // the ranking key of a sorted entry (make_key of its score and id)
+  auto key_of = [](uint64_t v) { return (v << 32) | (uint64_t)(uint32_t)(~(uint32_t)(v >> 32)); };
+  // positions from L on hold padding only (at least npow - L entries are ~0, all at the end)
+  for (int i = tid; i < L; i += nt) {
+    const uint64_t v = s_v[i];
+    int h = -1;  // an empty slot or a row of no group: never wins
+    if (v != ~0ull) {
+      const int g = group_of(group_off, n_groups, stride, s_first, s_samp, (int64_t)(v >> 32));
+      if (g >= 0) {
+        int64_t first = group_off[g];  // <= id
+        first = first < 0 ? 0 : first;
+        const uint64_t target = (uint64_t)first << 32;
+        int lo = 0, hi = i;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (s_v[mid] < target) lo = mid + 1;
+          else hi = mid;
+        }
+        h = lo;
+        atomicMax(&s_rmax[h], (unsigned long long)key_of(v));
+      }
+    }
+    s_head[i] = (int16_t)h;
+  }
+  __syncthreads();
+  for (int i = tid; i < L; i += nt) {
+    const int h = s_head[i];
+    uint64_t key = 0ull;
+    if (h >= 0) {
+      key = key_of(s_v[i]);
+      if (key != (uint64_t)s_rmax[h]) key = 0ull;
+    }
+    keys[(int64_t)q * L + i] = key;
+  }
+}
+
+// irc_topk_merge_grouped's workspace: the keys, then the Q + 1 list offsets of the select
+static size_t merge_keys_bytes(int64_t Q, int64_t L) { return align256((size_t)(Q * L) * 8); }
+static size_t merge_workspace_bytes(int64_t Q, int64_t L) {
+  return merge_keys_bytes(Q, L) + align256((size_t)(Q + 1) * 8);
+}
+static bool merge_sizes_ok(int64_t P, int64_t Q, int64_t kin) {
+  return P >= 1 && kin >= 1 && Q >= 0 && Q < (1ll << 31) - 1 && P <= S_STAGE &&
+         kin <= S_STAGE && P * kin <= S_STAGE;
+}
+
 // keys, and for the grouped form rmax and head after them: 8 bytes per candidate each, every
 // region on a 256-byte boundary
 static size_t region_bytes(int64_t n_cand) {
@@ -938,4 +1062,55 @@ extern "C" int irc_rerank_topk_grouped(const void* queries, const void* docs, in
                      (flags & IRC_RERANK_E4M3) != 0, true, group_off, n_groups},
                     queries, docs, Q, N, D, cand, cand_off, n_cand, k, doc_offset, score_scale,
                     workspace, workspace_bytes, out_score, out_idx, out_n, stream);
+}
+
+extern "C" int64_t irc_topk_merge_grouped_workspace(int64_t P, int64_t Q, int64_t kin) {
+  if (!merge_sizes_ok(P, Q, kin)) return 0;  // the call itself reports the sizes
+  return (int64_t)merge_workspace_bytes(Q, P * kin);
+}
+
+// The reduce step of the grouped candidate top-k over several shards: the collapse of each
+// query's P lists to one entry per group, then the select of rerank_run.
+extern "C" int irc_topk_merge_grouped(const float* in_score, const int64_t* in_idx, int64_t P,
+                                      int64_t Q, int64_t kin, int64_t kout,
+                                      const int64_t* group_off, int64_t n_groups,
+                                      void* workspace, int64_t workspace_bytes,
+                                      float* out_score, int64_t* out_idx, int32_t* out_n,
+                                      irc_stream_t stream) {
+  IRC_REQUIRE(P >= 1 && Q >= 0 && kin >= 1, "topk_merge_grouped: bad sizes");
+  IRC_REQUIRE(kout >= 1 && kout <= RR_MAXK, "topk_merge_grouped: kout=%lld outside [1, %d]",
+              (long long)kout, RR_MAXK);
+  IRC_REQUIRE(P <= S_STAGE && kin <= S_STAGE && P * kin <= S_STAGE,
+              "topk_merge_grouped: P * kin = %lld x %lld above %d entries per query",
+              (long long)P, (long long)kin, S_STAGE);
+  IRC_REQUIRE(Q < (1ll << 31) - 1, "topk_merge_grouped: Q too large");
+  IRC_REQUIRE(n_groups >= 0 && n_groups < (1ll << 31) - 1,
+              "topk_merge_grouped: n_groups=%lld outside [0, 2^31 - 1)", (long long)n_groups);
+  if (Q == 0) return IRC_OK;
+  IRC_REQUIRE(group_off != nullptr, "topk_merge_grouped: null group_off");
+  const int64_t L = P * kin;
+  const int64_t need = (int64_t)merge_workspace_bytes(Q, L);
+  IRC_REQUIRE(workspace != nullptr && workspace_bytes >= need,
+              "topk_merge_grouped: workspace %lld < required %lld bytes",
+              (long long)workspace_bytes, (long long)need);
+  IRC_REQUIRE(in_score && in_idx && out_score && out_idx && out_n,
+              "topk_merge_grouped: null pointer");
+  hipStream_t st = as_stream(stream);
+  uint64_t* keys = static_cast<uint64_t*>(workspace);
+  int64_t* list_off =
+      reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + merge_keys_bytes(Q, L));
+  // one thread per pair of sort slots (the sort array is L rounded up to a power of two)
+  int threads = 64;
+  while (threads < SNT && 2 * threads < L) threads <<= 1;
+  prof_begin(st);
+  hipLaunchKernelGGL(merge_collapse_kernel, dim3((unsigned)Q), dim3(threads), 0, st, in_score,
+                     in_idx, (int)P, (int)Q, (int)kin, group_off, (int)n_groups, keys, list_off);
+  // per entry: score + id read, key written
+  prof_end("topk_merge_collapse", st, (double)(Q * L) * 20.0);
+  if (int rc = check_launch("merge_collapse_kernel")) return rc;
+  prof_begin(st);
+  hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)Q), dim3(SNT), 0, st, keys, list_off,
+                     Q * L, (int)kout, out_score, out_idx, out_n);
+  prof_end("rerank_select", st, (double)(Q * L) * 8.0);
+  return check_launch("rerank_select_kernel");
 }

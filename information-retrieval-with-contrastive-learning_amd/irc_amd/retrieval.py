@@ -9,7 +9,10 @@ tfidf_doc_ranker.py:60-75); equal scores -> lower global doc index.
 Multi-GPU: the corpus is split into contiguous shards, one per
 rank, resident in HBM.  A search all-gathers the query embeddings over RCCL,
 scans the local shard (global indices via the shard offset), all-gathers the
-per-shard top-k lists and merges them with the same exact rule.
+per-shard top-k lists and merges them with the same exact rule.  The candidate-restricted
+top-k (``search_candidates``) is sharded the same way: the queries and their candidate lists
+are all-gathered, every shard ranks the candidates it owns, and the per-shard lists merge by
+``topk_merge``, or by ``topk_merge_grouped`` when the unit is a group of rows.
 """
 from __future__ import annotations
 
@@ -175,6 +178,42 @@ def topk_merge(scores: torch.Tensor, idx: torch.Tensor, k: int):
     return out_s, out_i
 
 
+def topk_merge_grouped(scores: torch.Tensor, idx: torch.Tensor, k: int,
+                       group_off: torch.Tensor, ws_tag: str = "merge"):
+    """Merge [P, Q, kin] per-shard GROUPED lists (``rerank_topk(..., group_off=)`` of P
+    shards) into the top-k distinct groups of the whole corpus (irc_topk_merge_grouped): of
+    the entries of one group -- its best row in each shard that returned it -- the best one
+    stays, equal scores keeping the lower row id.  ``idx`` holds global row ids, -1 in empty
+    slots; ``group_off`` as for ``rerank_topk``; P * kin <= 8192.  Returns (scores [Q, k],
+    idx [Q, k], n int32 [Q], groups int64 [Q, k]) as the grouped ``rerank_topk`` does."""
+    if group_off is None:
+        raise TypeError("group_off must be an int64 tensor, not None")
+    _check_group_off(group_off, scores)
+    require_hip(scores, idx, group_off)
+    s = contig(scores, torch.float32)
+    i = contig(idx, torch.int64)
+    if s.dim() != 3 or i.shape != s.shape:
+        raise ValueError(f"scores and idx must both be [P, Q, kin], not {tuple(s.shape)} and "
+                         f"{tuple(i.shape)}")
+    P, Q, kin = s.shape
+    go = group_off.contiguous()
+    out_s = torch.empty((Q, k), dtype=torch.float32, device=s.device)
+    out_i = torch.empty((Q, k), dtype=torch.int64, device=s.device)
+    out_n = torch.empty((Q,), dtype=torch.int32, device=s.device)
+    nbytes = int(_lib.fn("irc_topk_merge_grouped_workspace")(P, Q, kin))
+    ws = workspace(nbytes, s.device, ws_tag)
+    _lib.call("irc_topk_merge_grouped", ptr(s), ptr(i), P, Q, kin, k, ptr(go), go.numel() - 1,
+              ptr(ws), ws.numel(), ptr(out_s), ptr(out_i), ptr(out_n), stream_ptr(s.device))
+    return out_s, out_i, out_n, _groups_of(go, out_i)
+
+
+def _groups_of(group_off, idx):
+    """The group of every returned row (each lies in [group_off[0], group_off[-1])); -1 in
+    padded slots."""
+    groups = torch.searchsorted(group_off, idx, right=True) - 1
+    return torch.where(idx < 0, groups.new_full((), -1), groups)
+
+
 def __getattr__(name):
     # RERANK_CHUNK: the candidates one scoring workgroup of irc_rerank_topk takes, read from
     # the library (irc_rerank_chunk(), RR_CHUNK in csrc/rerank.hip) so it cannot drift; the
@@ -313,9 +352,9 @@ def rerank_topk(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
     int64 [Q, k] the group of each returned row (-1 in padded slots).  A row outside
     [group_off[0], group_off[-1]) is in no group and never returned.  The collapse needs
     ascending lists under both methods, so without ``ascending=True`` the lists are sorted
-    first under "gather" too.  It happens inside this one shard: a group whose rows lie
-    in two shards yields one winner per shard, and merging grouped results of several
-    shards is not built.  With ``group_off=None`` nothing changes."""
+    first under "gather" too.  It happens inside this one shard; the grouped results of
+    several shards merge with ``topk_merge_grouped``, which keeps one row of a group whose
+    rows lie in two shards.  With ``group_off=None`` nothing changes."""
     if method not in RERANK_METHODS:
         raise ValueError(f"method must be one of {RERANK_METHODS}, not {method!r}")
     _check_group_off(group_off, queries)
@@ -381,10 +420,7 @@ def _rerank_call(q, d, cand, cand_off, k, doc_offset, score_scale, ws_tag, metho
     _lib.call("irc_rerank_topk_grouped", ptr(q), ptr(d), Q, N, D, ptr(c), ptr(off), n_cand, k,
               doc_offset, ptr(go), n_groups, flags, score_scale, ptr(ws), ws.numel(),
               ptr(out_s), ptr(out_i), ptr(out_n), stream_ptr(q.device))
-    # every returned row lies in [group_off[0], group_off[-1]); a padded slot is -1
-    groups = torch.searchsorted(go, out_i, right=True) - 1
-    groups = torch.where(out_i < 0, groups.new_full((), -1), groups)
-    return out_s, out_i, out_n, groups
+    return out_s, out_i, out_n, _groups_of(go, out_i)
 
 
 def rerank_topk_fp8(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
@@ -439,9 +475,10 @@ class ShardedDenseIndex:
     """One rank's HBM-resident shard of the corpus embedding matrix.
 
     ``docs`` is this rank's shard [N_local, D] (bf16), ``doc_offset`` its first
-    global index.  ``search`` is collective over ``group`` when one is given:
-    every rank passes its local query slice (may be empty) and receives the
-    global top-k for ALL gathered queries (queries ordered by rank).
+    global index.  ``search`` and ``search_candidates`` are collective over
+    ``group`` when one is given: every rank passes its local query slice (may be
+    empty) and receives the global top-k for ALL gathered queries (queries
+    ordered by rank).
 
     ``dtype="fp8"`` keeps the shard as e4m3 bytes (half the HBM bytes per scan,
     BASELINE config C5): queries are quantised with the same power-of-two
@@ -538,10 +575,27 @@ class ShardedDenseIndex:
                           method: str = "gather", ascending: bool = False, group_off=None):
         """Top-k of each query over its own candidate docs only (global ids, the CSR pair
         ``SparseIndex.candidates`` / ``expand_ranges`` leave on the device): (scores
-        [Q, k], idx [Q, k], n [Q]) as ``rerank_topk``.  Single process; bf16 and fp8 shards
-        (on an fp8 index the queries are quantised with ``fp8_scale`` and ``rerank_topk_fp8``
-        ranks the e4m3 codes, scores descaled exactly as ``search`` descales them; the
-        measured fp8 tables are in DESIGN.md 6e).
+        [Q, k], idx [Q, k], n [Q]) as ``rerank_topk``.  bf16 and fp8 shards (on an fp8 index
+        the queries are quantised with ``fp8_scale`` and ``rerank_topk_fp8`` ranks the e4m3
+        codes, scores descaled exactly as ``search`` descales them; the measured fp8 tables
+        are in DESIGN.md 6e).
+
+        Collective over ``group`` as ``search`` is, in the same three steps: (1) every rank
+        passes its own query slice (may be empty) and the CSR pair of those queries'
+        candidates; one count exchange carries (queries, candidates) per rank, then the
+        queries, the candidate ids (as int32, the kernels' dtype, so the ranks need not
+        agree on int32 against int64) and the list lengths are all-gathered in rank order
+        and ``cand_off`` is rebuilt for the gathered batch; (2) every rank ranks the
+        candidates its shard owns (ids of other shards are skipped by the kernels); (3) the
+        per-shard lists are all-gathered and merged, by ``topk_merge`` or, with
+        ``group_off``, by ``topk_merge_grouped`` (k * world size <= 8192 there).  Every rank
+        receives the result for ALL gathered queries, in rank order.  The argument checks
+        (``method``, ``group_off``, the dtype of ``cand``, the length of ``cand_off``, the
+        queries' width) run on each rank's own arguments BEFORE the first collective: a bad
+        argument raises on that rank at once and never leaves the others waiting in a
+        gather it does not join (they fail on the collective's timeout instead of
+        computing with half a batch).  Every rank passes queries of one dtype, the same
+        ``k``, ``method`` and ``group_off``.
 
         ``method``: "gather" (the default), "stream", or "auto", which takes
         ``rerank_method``'s choice when ``ascending=True`` and "gather" otherwise;
@@ -549,9 +603,9 @@ class ShardedDenseIndex:
 
         ``group_off`` (int64 [n_groups + 1], global row ids, on the queries' device): the
         top-k distinct groups, each by its best row, and a fourth result ``groups`` [Q, k],
-        as ``rerank_topk`` documents it; "auto" chooses as without it.  The collapse
-        happens inside this one shard: a group whose rows lie in two shards yields one
-        winner per shard (the multi-shard merge of grouped results is not built).
+        as ``rerank_topk`` documents it; "auto" chooses as without it.  Over a process
+        group the result is the grouped top-k of the whole corpus: merging the per-shard
+        grouped lists is exact ("Across shards").
 
         Cost model: "gather" reads the candidate rows whole, once per
         (query, candidate), with no reuse across queries -- n_cand * D * 2 bytes -- while
@@ -592,11 +646,22 @@ class ShardedDenseIndex:
             # damaged header on load()
             raise ValueError("fp8 index: the shard is not e4m3 bytes (torch.uint8) but "
                              f"{self.docs.dtype}")
-        if self._sharded():
-            raise NotImplementedError(
-                "search_candidates over a process group: the all_gather of the queries and "
-                "candidate lists and of the per-shard top-k lists (search()'s collectives) "
-                "is not built; the per-shard rerank_topk call already skips foreign ids")
+        if not self._sharded():
+            return self._local_candidates(queries, cand, cand_off, k, ws_tag, method, ascending,
+                                          group_off)
+        c, off = self._own_candidates(queries, cand, cand_off, method)  # raises before (1)
+        allq, allc, alloff = self._gather_candidates(queries, c, off)  # (1)
+        out = self._local_candidates(allq, allc, alloff, k, ws_tag, method, ascending,
+                                     group_off)  # (2)
+        return self._exchange_merge_candidates(out[0], out[1], k, group_off)  # (3)
+
+    # The steps of a sharded search_candidates are methods as search()'s are, so the
+    # collective orchestration runs on CPU (gloo) with test doubles for the device calls
+    # (tests/test_rerank_sharded_cpu.py): _local_candidates, _merge, _merge_grouped.
+    def _local_candidates(self, queries, cand, cand_off, k, ws_tag="rerank", method="gather",
+                          ascending=False, group_off=None):
+        """This shard's candidate top-k: the whole of a single-process search_candidates,
+        step (2) of a sharded one."""
         if method == "auto":
             # the stream method's sort of unsorted lists is not in the measured crossovers
             method = "gather" if not ascending else rerank_method(
@@ -609,6 +674,79 @@ class ShardedDenseIndex:
                                    method=method, ascending=ascending, group_off=group_off)
         return rerank_topk(queries, self.docs, cand, cand_off, k, self.doc_offset, ws_tag=ws_tag,
                            method=method, ascending=ascending, group_off=group_off)
+
+    def _merge_grouped(self, scores, idx, k, group_off):
+        return topk_merge_grouped(scores, idx, k, group_off)
+
+    def _own_candidates(self, queries, cand, cand_off, method):
+        """This rank's arguments checked as the local call would check them, before any
+        collective; returns the ids as flat int32 (an int64 id outside int32 is in no shard
+        and is clamped to -1 / 2^31 - 1, which keeps an ascending list ascending) and the
+        offsets as int64."""
+        if method != "auto" and method not in RERANK_METHODS:
+            raise ValueError(f"method must be 'auto' or one of {RERANK_METHODS}, not {method!r}")
+        if queries.dim() != 2 or queries.shape[1] != self.docs.shape[1]:
+            raise ValueError(f"dim mismatch: queries {tuple(queries.shape)}, docs "
+                             f"D={self.docs.shape[1]}")
+        if cand.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"cand must be int32 or int64, not {cand.dtype}")
+        if cand_off.numel() != queries.shape[0] + 1:
+            raise ValueError(f"cand_off has {cand_off.numel()} entries for {queries.shape[0]} "
+                             "queries (Q + 1)")
+        if cand.dtype == torch.int64:
+            cand = cand.clamp(-1, 2 ** 31 - 1)
+        return (cand.reshape(-1).to(torch.int32).contiguous(),
+                cand_off.reshape(-1).to(torch.int64).contiguous())
+
+    def _gather_candidates(self, queries, cand, cand_off):
+        """(1) every rank's query slice and candidate lists, all-gathered in rank order:
+        (queries [Q_all, D], cand int32 [n_all], cand_off int64 [Q_all + 1]).  One count
+        exchange (a host sync) carries each rank's (queries, candidates); the offsets are
+        rebuilt from the gathered list lengths."""
+        import torch.distributed as dist
+
+        world = dist.get_world_size(self.group)
+        mine = torch.tensor([queries.shape[0], cand.numel()], dtype=torch.int64,
+                            device=queries.device)
+        cnt = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(cnt, mine, group=self.group)
+        cnt = torch.stack(cnt).cpu().tolist()
+        nq, nc = [c[0] for c in cnt], [c[1] for c in cnt]
+        allq = self._gather_ragged(queries, nq)
+        allc = self._gather_ragged(cand, nc)
+        lengths = self._gather_ragged(cand_off[1:] - cand_off[:-1], nq)
+        alloff = torch.cat([lengths.new_zeros(1), torch.cumsum(lengths, 0)])
+        return allq, allc, alloff
+
+    def _gather_ragged(self, x, counts):
+        """Every rank's ``x`` ([counts[rank], ...]) concatenated along dim 0 in rank order:
+        padded to the longest, all-gathered, cut back."""
+        import torch.distributed as dist
+
+        top = max(counts)
+        pad = x.contiguous()
+        if top != x.shape[0]:
+            pad = torch.zeros((top,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+            pad[: x.shape[0]] = x
+        parts = [torch.empty_like(pad) for _ in counts]
+        dist.all_gather(parts, pad, group=self.group)
+        return torch.cat([p[:c] for p, c in zip(parts, counts)], dim=0)
+
+    def _exchange_merge_candidates(self, s, i, k, group_off=None):
+        """(3) every shard's candidate top-k lists all-gathered and merged: by the scan's
+        rule (n = the filled slots), or per group -- a group whose best rows lie in two
+        shards is in two lists, and only its best row stays."""
+        import torch.distributed as dist
+
+        world = dist.get_world_size(self.group)
+        ss = [torch.empty_like(s) for _ in range(world)]
+        ii = [torch.empty_like(i) for _ in range(world)]
+        dist.all_gather(ss, s.contiguous(), group=self.group)
+        dist.all_gather(ii, i.contiguous(), group=self.group)
+        if group_off is not None:
+            return self._merge_grouped(torch.stack(ss), torch.stack(ii), k, group_off)
+        ms, mi = self._merge(torch.stack(ss), torch.stack(ii), k)
+        return ms, mi, (mi >= 0).sum(dim=1).to(torch.int32)
 
     # The three steps of a sharded search, separately callable (bench.py times each).
     def _sharded(self):

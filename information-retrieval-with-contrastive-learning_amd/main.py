@@ -11,15 +11,15 @@ Multi-GPU (one process per GPU):
 When the launcher sets WORLD_SIZE > 1, the process group is initialised over RCCL
 (backend "nccl") on cuda:LOCAL_RANK before any other GPU call; training is data
 parallel (each rank a disjoint slice of the pairs, global in-batch negatives,
-gradient all-reduce; logging and checkpoints on rank 0) and ``--retrieval dense``
-shards the evidence corpus over the ranks.  IRC_DIST_BACKEND=gloo selects gloo
+gradient all-reduce; logging and checkpoints on rank 0) and ``--retrieval dense`` /
+``--retrieval hybrid`` shard the evidence corpus over the ranks.  IRC_DIST_BACKEND=gloo selects gloo
 (tests that share one GPU between ranks).
 
 --data doc trains (src.train.train); --data fever runs src.evaluation.predict:
 the reference's sparse candidate filter per claim (default) or, with
 ``--retrieval dense``, the bi-encoder's exact top-k over the evidence corpus, or, with
 ``--retrieval hybrid``, that top-k over each claim's filter candidates only (the
-reference's two stages joined; single process; ``--rerank-unit page`` ranks the k best
+reference's two stages joined; ``--rerank-unit page`` ranks the k best
 pages, each by its best line, instead of the k best lines).  The compute runs on the
 MI355X HIP kernels only:
 ``--gpu -1`` (CPU) is rejected -- there is no CPU fallback in this build.

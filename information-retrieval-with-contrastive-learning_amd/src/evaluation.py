@@ -12,7 +12,8 @@ claim batch scored against all of them with the exact top-k scan
 evidence recall@k printed.  ``--retrieval hybrid`` joins the two as the reference's
 predict() describes: the filter's candidates (:57-83) stay on the device and the
 dense scores (:110-112) rank each claim's candidates only (``hybrid_search``,
-irc_rerank_topk).
+irc_rerank_topk); under a launcher the corpus is sharded over the ranks as for
+``--retrieval dense`` and the per-shard lists are merged.
 """
 import pickle
 import time
@@ -179,12 +180,22 @@ def hybrid_search(model, dense_index, sparse_index, row_off, claims, k, device,
     "stream" or "auto" (``ShardedDenseIndex.search_candidates``); the row lists are
     ascending by construction, which the stream method needs.  ``group_off`` (int64
     [n_groups + 1] on the device; ``row_off`` itself for pages): the top-k distinct groups,
-    each by its best row, and a fourth value groups [Q, k] (``rerank_topk``)."""
+    each by its best row, and a fourth value groups [Q, k] (``rerank_topk``).
+
+    Over a sharded ``dense_index`` (one with a process group) the call is collective:
+    ``claims`` is this rank's slice of the batch (may be empty), ``row_off`` / ``group_off``
+    stay in global row ids, and the result covers the whole batch, in rank order
+    (``ShardedDenseIndex.search_candidates``)."""
     from irc_amd.retrieval import expand_ranges
 
-    q = model.ctx2vec(claims, device)
-    cand, off = sparse_index.candidates(claims, bigram_only)
-    rows, rows_off = expand_ranges(cand, off, row_off)
+    if claims:
+        q = model.ctx2vec(claims, device)
+        cand, off = sparse_index.candidates(claims, bigram_only)
+        rows, rows_off = expand_ranges(cand, off, row_off)
+    else:  # a rank with no claim of this batch still joins the collectives
+        q = torch.empty((0, dense_index.docs.shape[1]), dtype=torch.float32, device=device)
+        rows = torch.empty(0, dtype=torch.int64, device=device)
+        rows_off = torch.zeros(1, dtype=torch.int64, device=device)
     if group_off is None:
         return dense_index.search_candidates(q, rows, rows_off, k, method=method, ascending=True)
     return dense_index.search_candidates(q, rows, rows_off, k, method=method, ascending=True,
@@ -196,13 +207,23 @@ def predict_hybrid(args, k=100):
     """The reference's two-stage predict: per claim batch the hashed n-gram filter, then
     the bi-encoder's exact top-k over the filter's candidates only.  Prints each batch's
     latency and the evidence recall@k (a claim with no candidates is a miss); returns
-    recall@k.  Single process.  ``args.rerank_method`` (default "auto") picks the scoring
-    method per batch; the ranking contract is the same either way.  ``args.index_dtype``
-    (default "bf16"): "fp8" keeps the corpus as e4m3 bytes and ranks the quantised embeddings."""
+    recall@k.  ``args.rerank_method`` (default "auto") picks the scoring method per batch;
+    the ranking contract is the same either way.  ``args.index_dtype`` (default "bf16"):
+    "fp8" keeps the corpus as e4m3 bytes and ranks the quantised embeddings.
+
+    Under data parallelism (``args.dist_group``, main.py under torchrun) the corpus is
+    sharded as in ``predict_dense``: rank r encodes and keeps only its contiguous slice of
+    the rows, each claim batch is split over the ranks, every rank embeds and filters its
+    own claims (the count matrix is small and replicated; ``row_off`` stays in global row
+    ids) and ``search_candidates`` gathers the lists, ranks each shard's own candidates and
+    merges -- per page with ``--rerank-unit page``.  Every rank receives the whole batch's
+    result and scores recall over it; rank 0 prints."""
+    from irc_amd.retrieval import shard_bounds
+
     assert args.ckpt is not None
-    if getattr(args, "dist_group", None) is not None and int(getattr(args, "world_size", 1)) > 1:
-        raise NotImplementedError("--retrieval hybrid runs in a single process: the collective "
-                                  "around search_candidates is not built")
+    group = getattr(args, "dist_group", None)
+    world = int(getattr(args, "world_size", 1)) if group is not None else 1
+    rank = int(getattr(args, "rank", 0)) if group is not None else 0
     _, model, _, _ = load_model(args.ckpt)
     model = model.to(args.device).eval()
     loader = get_dataloader(args, train=False, distributed=False)
@@ -214,23 +235,29 @@ def predict_hybrid(args, k=100):
     sparse_index = SparseIndex(count_matrix, ngram=metadata["ngram"], device=args.device)
     titles, texts, row_off = hybrid_corpus(loader.dataset.wiki, metadata["doc_dict"][1])
     row_off = torch.tensor(row_off, dtype=torch.int64, device=args.device)
-    index = ShardedDenseIndex(encode_corpus(model, texts, args.device),
+    lo, hi = shard_bounds(len(texts), world, rank)
+    index = ShardedDenseIndex(encode_corpus(model, texts[lo:hi], args.device), doc_offset=lo,
+                              group=group,
                               dtype=getattr(args, "index_dtype", "bf16"))  # main.py --index-dtype
     method = getattr(args, "rerank_method", "auto")  # main.py --rerank-method
     # main.py --rerank-unit: "page" ranks each claim's k best pages, each by its best line
     # (row_off is the page -> row range map), so recall@k is over k pages
     by_page = getattr(args, "rerank_unit", "line") == "page"
     hits = total = 0
-    for batch in tqdm(loader, desc="Iteration"):
+    for batch in tqdm(loader, desc="Iteration", disable=rank != 0):
         claims = [d["claim"] for d in batch]
         s = time.time()
-        idx = hybrid_search(model, index, sparse_index, row_off, claims, k, args.device,
+        c0, c1 = shard_bounds(len(claims), world, rank)
+        # rows: the whole batch, in order
+        idx = hybrid_search(model, index, sparse_index, row_off, claims[c0:c1], k, args.device,
                             method=method, group_off=row_off if by_page else None)[1]
         torch.cuda.synchronize()
-        print(f"batch of {len(claims)} claims: {time.time() - s:.4f}s")
+        if rank == 0:
+            print(f"batch of {len(claims)} claims: {time.time() - s:.4f}s")
         for d, row in zip(batch, idx.cpu().tolist()):
             gold = {e["title"] for e in d["evidences"]}
             hits += int(any(titles[j] in gold for j in row if j >= 0))
             total += 1
-    print(f"evidence recall@{k}{' (pages)' if by_page else ''}: {hits / max(total, 1):.4f}")
+    if rank == 0:
+        print(f"evidence recall@{k}{' (pages)' if by_page else ''}: {hits / max(total, 1):.4f}")
     return hits / max(total, 1)

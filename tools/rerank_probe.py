@@ -8,6 +8,8 @@ cross.
     python tools/rerank_probe.py --tables profiles/rerank_fp8_probe.json  # + fp8 / bf16 table
     python tools/rerank_probe.py --grouped [--dtype fp8]   # top-k per group, see below
     python tools/rerank_probe.py --tables profiles/rerank_group_probe.json
+    python tools/rerank_probe.py --merge > profiles/rerank_merge_probe.json  # see below
+    python tools/rerank_probe.py --tables profiles/rerank_merge_probe.json
 
 One MI355X, the C3 shard (250k x 768 bf16, larger than the Infinity Cache), random
 ascending candidate lists of 0.1 / 1 / 5 / 25 % of the shard per query, Q in {1, 16, 64,
@@ -32,6 +34,11 @@ constants of retrieval.rerank_method(dtype="fp8").
 pages of a fixed-seed draw, mean about 10 rows) alternating with the ungrouped call, gathered
 and streamed; profiles/rerank_group_probe.json holds the bf16 and the fp8 run's lines under
 "bf16" and "fp8".
+``--merge``: the reduce step of a sharded call, no scoring: Q = 256 queries, P per-shard
+lists of kin = kout entries each, P x kin in (2, 100), (8, 100), (8, 1024) -- the call time
+of topk_merge (irc_topk_merge) and of topk_merge_grouped (irc_topk_merge_grouped) on the
+same lists, alternating window by window, and the grouped merge's two kernels from a
+profiled pass.  What the merge adds to a sharded search_candidates.
 Prints a table to stderr and ONE JSON line to stdout."""
 import argparse
 import ctypes
@@ -281,10 +288,115 @@ def grouped_probe(args):
                       "cells": cells}))
 
 
+def merge_tables(r):
+    """The table of DESIGN.md 6e "Across shards": per shape the two merges' call times and
+    the grouped merge's kernels."""
+    print(f"Q = {r['Q']}, {r['n_groups']:,} groups over {r['N']:,} rows\n")
+    print("| shards P | kin = kout | entries / query | topk_merge call | topk_merge_grouped call | "
+          "ratio | collapse kernel | select kernel |\n|---|---|---|---|---|---|---|---|")
+    for c in r["cells"]:
+        print(f"| {c['P']} | {c['kin']:,} | {c['P'] * c['kin']:,} | {c['merge_call_us']:,.1f} | "
+              f"{c['merge_grouped_call_us']:,.1f} | {c['ratio']:.2f} | "
+              f"{c['collapse_kernel_us']:,.1f} | {c['select_kernel_us']:,.1f} |")
+    print()
+    worst = max(r["cells"], key=lambda c: max(c["spread_pct"].values()))
+    print(f"largest min-max spread of a cell's windows: {max(worst['spread_pct'].values()):.2f}% "
+          f"(P = {worst['P']}, kin = {worst['kin']}); rounds per cell: {r['rounds']}")
+
+
+MERGE_SHAPES = ((2, 100), (8, 100), (8, 1024))
+
+
+def merge_probe(args):
+    """--merge: topk_merge and topk_merge_grouped on the same [P, Q, kin] lists, as P shards
+    of an N-row corpus would return them for Q = 256 queries: list p holds kin distinct rows
+    of shard p by descending score, unit-normal scores rounded to 1/64 (ties), pages of the
+    fixed-seed draw of --grouped (mean about 10 rows).  Windows of back-to-back calls, the two
+    alternating round by round (median over the rounds); the grouped merge's kernels from a
+    profiled pass of their own.  ONE JSON line to stdout."""
+    from irc_amd import _lib, retrieval
+
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(2025)
+    Q = 256
+    sizes = 1 + torch.empty(args.n, dtype=torch.float64).exponential_(1 / 9.5, generator=g).long()
+    ends = torch.cumsum(sizes, 0)
+    ends = ends[: int((ends < args.n).sum())]
+    group_off = torch.cat([torch.zeros(1, dtype=torch.int64), ends,
+                           torch.tensor([args.n])]).to(dev)
+    torch.manual_seed(2025)
+    cells = []
+    for P, kin in MERGE_SHAPES:
+        sets = []
+        for _ in range(args.sets):
+            idx = torch.empty((P, Q, kin), dtype=torch.int64, device=dev)
+            for p in range(P):
+                lo, hi = retrieval.shard_bounds(args.n, P, p)
+                idx[p] = lo + torch.rand(Q, hi - lo, device=dev).topk(kin, dim=1).indices
+            sc = (torch.randn(P, Q, kin, device=dev) * 64).round() / 64
+            sets.append((sc.sort(dim=2, descending=True).values.contiguous(), idx))
+
+        def make(grouped):
+            counter = [0]
+
+            def call():
+                counter[0] += 1
+                sc, idx = sets[counter[0] % args.sets]
+                if grouped:
+                    return retrieval.topk_merge_grouped(sc, idx, kin, group_off)
+                return retrieval.topk_merge(sc, idx, kin)
+            return call
+
+        timed = [("merge", make(False)), ("merge_grouped", make(True))]
+        est = {}
+        for name, fn in timed:
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            est[name] = _window_ms(fn, 5)
+        reps = {m: max(2 * args.sets, min(4000, int(args.window_ms / max(est[m], 1e-3))))
+                for m in est}
+        for m in reps:
+            reps[m] -= reps[m] % args.sets  # every draw equally often
+        t = {m: [] for m, _ in timed}
+        for _ in range(args.rounds):  # alternate them window by window
+            for m, fn in timed:
+                t[m].append(_window_ms(fn, reps[m]))
+        lib.irc_prof_reset()
+        lib.irc_prof_enable(1)
+        for _ in range(min(reps["merge_grouped"], 12 * args.sets)):
+            timed[1][1]()
+        torch.cuda.synchronize()
+        lib.irc_prof_enable(0)
+        collapse_us, _ = _prof(lib, b"topk_merge_collapse")
+        select_us, _ = _prof(lib, b"rerank_select")
+        med = {m: statistics.median(t[m]) * 1e3 for m in t}
+        n_out = retrieval.topk_merge_grouped(*sets[0], kin, group_off)[2].float().mean().item()
+        cell = {"P": P, "kin": kin, "kout": kin, "ratio": med["merge_grouped"] / med["merge"],
+                "collapse_kernel_us": collapse_us, "select_kernel_us": select_us,
+                "mean_groups_returned": n_out, "reps": reps,
+                "spread_pct": {m: 100.0 * (max(t[m]) - min(t[m])) / statistics.median(t[m])
+                               for m in t}}
+        for m in t:
+            cell[f"{m}_call_us"] = med[m]
+            cell[f"{m}_call_us_minmax"] = [min(t[m]) * 1e3, max(t[m]) * 1e3]
+        cells.append(cell)
+        print(f"P={P} kin={kin:5d}  topk_merge {med['merge']:8.1f} us  topk_merge_grouped "
+              f"{med['merge_grouped']:8.1f} us ({cell['ratio']:.2f})  collapse {collapse_us:7.1f} us "
+              f"select {select_us:7.1f} us", file=sys.stderr, flush=True)
+    print(json.dumps({"probe": "rerank_merge", "device": torch.cuda.get_device_name(0),
+                      "Q": Q, "N": args.n, "rounds": args.rounds, "window_ms": args.window_ms,
+                      "sets": args.sets, "n_groups": int(group_off.numel() - 1),
+                      "cells": cells}))
+
+
 def main():
     if len(sys.argv) == 3 and sys.argv[1] == "--tables":
         with open(sys.argv[2]) as f:
             rec = json.load(f)
+        if isinstance(rec, dict) and rec.get("probe") == "rerank_merge":
+            return merge_tables(rec)
         if isinstance(rec, dict) and rec.get("probe") == "rerank_grouped":
             return grouped_tables(rec)
         if isinstance(rec, dict) and "bf16" in rec and "fp8" in rec:  # the two grouped runs
@@ -306,10 +418,14 @@ def main():
                     help="fp8: the e4m3 calls, with the bf16 calls of the same cells alongside")
     ap.add_argument("--grouped", action="store_true",
                     help="time rerank_topk(group_off=...) next to the ungrouped call")
+    ap.add_argument("--merge", action="store_true",
+                    help="time topk_merge and topk_merge_grouped on the same per-shard lists")
     args = ap.parse_args()
     fp8 = args.dtype == "fp8"
     if not torch.cuda.is_available():
         raise SystemExit("rerank_probe measures on a HIP device; none is visible")
+    if args.merge:
+        return merge_probe(args)
     if args.grouped:
         return grouped_probe(args)
     from irc_amd import _lib, retrieval
