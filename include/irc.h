@@ -224,6 +224,48 @@ int irc_topk_merge_grouped(const float* in_score, const int64_t* in_idx, int64_t
                            float* out_score, int64_t* out_idx, int32_t* out_n,
                            irc_stream_t stream);
 
+/* The dense scan per GROUP of rows (per page): the top-k distinct groups of the WHOLE shard,
+ * each by its best row.  Every row is a candidate of every query, so there is no list: the
+ * shard streams once per 256-query tile through the MFMA GEMM loop, as in
+ * irc_rerank_topk_stream, and the loop's epilogue folds each score tile into one ranking key
+ * per (query, group) (gemm_pp.hip, EPI_GROUP); irc_rerank_topk's select ranks those keys.
+ *
+ * group_off [n_groups + 1] int64, non-decreasing, in GLOBAL row ids: group g is the rows
+ * [group_off[g], group_off[g + 1]); repeated values are empty groups.  Shard rows outside
+ * [group_off[0], group_off[n_groups]) are in no group and are never returned.  A group may
+ * begin before doc_offset or end past doc_offset + N: only its rows in this shard count, and
+ * irc_topk_merge_grouped joins the halves that two shards return.  A group_off that is not
+ * non-decreasing may be ranked wrongly; nothing is read or written out of bounds.
+ *
+ * Per query the output is the groups with a row in the shard, each by its best row -- ties
+ * within a group keep the lower row id -- ordered by (score desc, row id asc),
+ * irc_rerank_topk_grouped's rule.  out_idx holds global row ids, out_n[q] = min(k, groups
+ * with a row in the shard), the slots past it are (-inf, -1).  Exact and deterministic: the
+ * only atomics are 64-bit integer maxima of keys.  The score of a (query, row) is
+ * irc_rerank_topk_stream's bit for bit (the same loop and tile origins); with
+ * flags = IRC_RERANK_E4M3 the operands are e4m3 bytes and the score is the raw sum times
+ * score_scale, as irc_rerank_topk_stream_fp8 reports it (D % 128 == 0).  No other flag.
+ *
+ * Workspace (irc_scan_topk_grouped_workspace, 0 for sizes the call rejects): the keys
+ * [Q][n_groups], zeroed by the call with one memset, and the select's Q + 1 list offsets:
+ * align256(Q * n_groups * 8) + align256((Q + 1) * 8) bytes.  Its contents before the call do
+ * not matter.
+ *
+ * Validation, in this order, each IRC_E_INVALID with a message that starts
+ * "scan_topk_grouped:" and found before any device work: Q, N >= 0; 1 <= k <= 1024; D as
+ * irc_scan_topk accepts; e4m3 needs D % 128 == 0; no flag but IRC_RERANK_E4M3; an e4m3
+ * score_scale is a power of two; doc_offset >= 0 and doc_offset + N < 2^31; Q < 2^31 - 1;
+ * 0 <= n_groups < 2^31 - 1; Q * n_groups < 2^39; ceil(Q / 256) * ceil(N / 256) < 2^31; then
+ * the workspace (IRC_E_WORKSPACE).  Q == 0 returns IRC_OK there and touches nothing; else no
+ * null array (docs may be null when N == 0) and queries / docs 16-byte aligned.  With N == 0
+ * or n_groups == 0 every output slot is padding and out_n is 0. */
+int64_t irc_scan_topk_grouped_workspace(int64_t Q, int64_t n_groups, int64_t k);
+int irc_scan_topk_grouped(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,
+                          int64_t k, int64_t doc_offset, const int64_t* group_off,
+                          int64_t n_groups, uint32_t flags /* IRC_RERANK_E4M3 only */,
+                          float score_scale, void* workspace, int64_t workspace_bytes,
+                          float* out_score, int64_t* out_idx, int32_t* out_n, irc_stream_t stream);
+
 /* Raw score tile for tests / diagnostics: out[Q, N] fp32 = queries . docs^T
  * using the same MFMA path as irc_scan_topk. */
 int irc_scan_scores(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,

@@ -93,6 +93,15 @@ struct PArgs {
   // e4m3 pick (run_pick with fp8): the key's score is C[q][doc] * score_scale, a power of
   // two (exact); the bf16 pick does not read it
   float score_scale;
+  // group maximum (EPI_GROUP, run_group): every doc of the shard is a candidate of every
+  // query.  Group g owns the global doc ids [group_off[g], group_off[g + 1]) (non-decreasing,
+  // n_groups + 1 entries); gmax[q * n_groups + g], zeroed by the caller, receives the
+  // maximum of make_key(C[q][id - doc_offset] (* score_scale for fp8), id) over the ids of
+  // group g in this shard, by plain stores and 64-bit integer atomic maxima only.  A doc of
+  // no group touches nothing.  doc_offset and score_scale as for the pick.
+  uint64_t* gmax;
+  const int64_t* group_off;
+  int n_groups;
 };
 
 int splits_for(int out_f32, int epi, int64_t M, int64_t N, int64_t K, int64_t batch,
@@ -115,6 +124,10 @@ void run_scan(const PArgs& a, hipStream_t st, bool fp8 = false);
 void run_pick(const PArgs& a, hipStream_t st, bool fp8 = false);
 // doc-tile width of run_pick
 constexpr int PICK_TILE = 256;
+// group maximum: A = queries [M=Q][K=D], B = docs [N][D], EPI_GROUP (see PArgs), the launch
+// shape, main loop and tile origins of run_pick, so the accumulators of a (query, doc) are
+// the pick's bit for bit; M, N, n_groups > 0, the same tile-count limit, fp8 as run_pick
+void run_group(const PArgs& a, hipStream_t st, bool fp8 = false);
 // raw fp32 C = A . B^T of e4m3 operands (K, lda, ldb in 2-byte units; vec_c layout)
 void run_scores_fp8(const PArgs& a, hipStream_t st);
 // e4m3 linear layer: bf16 C = (A8 . B8^T) * sa[m] * sb[n] (+ bias / GELU / residual);

@@ -913,6 +913,138 @@ __device__ __forceinline__ void epilogue_pick(const PArgs& g, const f32x4 (&acc)
   }
 }
 
+// Group maximum (EPI_GROUP, irc_scan_topk_grouped): the pick's tile with EVERY doc a
+// candidate of every query, folded into one key per (query, group) instead of one per
+// (query, doc): no list to read, 8 bytes per (query, group) to write.  BEFORE the main loop
+// each of the first 256 threads finds the group of its column's global id (group_of: the
+// search starts from 256 samples of group_off, kept in the first 2 KB of the K-tile buffers,
+// which nothing uses yet) and writes its index, or -1 for a column past N or in no group,
+// into a 256-entry map in the LDS past the two K-major K-tile buffers (the pick's place).
+// A tile with no column in a group returns there.
+constexpr int GROUP_OFF = PICK_OFF;
+static_assert(GROUP_OFF + BN * 4 + 16 <= LDS_BYTES, "group map past the K-tile buffers");
+static_assert(BN == RC_NS, "one sample of group_off per thread of the map");
+
+// the group of each of the tile's columns -> LDS; false: no column is in a group
+// (workgroup-uniform)
+__device__ __forceinline__ bool group_map(const PArgs& g, char* lds, int n0) {
+  int64_t* samp = reinterpret_cast<int64_t*>(lds);  // RC_NS samples, then group_off[0]
+  int* gmap = reinterpret_cast<int*>(lds + GROUP_OFF);
+  int* any = gmap + BN;
+  const int tid = threadIdx.x;
+  const int64_t stride = ((int64_t)g.n_groups + RC_NS - 1) / RC_NS;
+  if (tid < RC_NS) {
+    const int64_t at = (tid + 1) * stride;
+    samp[tid] = g.group_off[at < g.n_groups ? at : g.n_groups];
+  }
+  if (tid == RC_NS) {
+    samp[RC_NS] = g.group_off[0];
+    *any = 0;
+  }
+  lds_barrier();
+  if (tid < BN) {
+    int gi = -1;
+    if (n0 + tid < g.N) {
+      gi = group_of(g.group_off, g.n_groups, stride, samp[RC_NS], samp, g.doc_offset + n0 + tid);
+      // a group_off that is not non-decreasing may send the search anywhere: the index
+      // addresses gmax, so it stays below n_groups whatever the array holds
+      gi = gi < g.n_groups ? gi : g.n_groups - 1;
+    }
+    gmap[tid] = gi;
+    if (gi >= 0) *any = 1;
+  }
+  lds_barrier();  // also: every reader is done with the samples before the K-tile DMA
+  return *any != 0;
+}
+
+// Four passes of 64 queries, staged exactly as epilogue_pick stages them.  Then the 8 lanes
+// of thread group t >> 3 walk query t >> 3's 256 columns, lane s the 32 consecutive columns
+// from 32 s (consecutive in S too: the flip moves the whole aligned span).  A run is a
+// maximal stretch of one group index in the lane's span; the lane keeps the maximum of the
+// run's keys -- make_key(score, id): equal scores keep the lower id -- and folds it into
+// gmax[q][group] when the run ends.  A run whose group has no column in any other lane's
+// span or any other tile -- the map entries beside it differ, and it does not touch the
+// tile's first (unless the shard starts there) or last column -- is the only writer of its
+// slot in the whole launch and stores it; every other run (a group cut by a lane span or a
+// tile edge) folds with one 64-bit integer atomic max, which does not depend on the order
+// the atomics land in.  No float is compared outside make_key, nothing reads gmax.
+template <int F8>
+__device__ __forceinline__ void epilogue_group(const PArgs& g, const f32x4 (&acc)[8][4],
+                                               char* lds, int m0, int n0, int grp, int wn,
+                                               int lane) {
+  float* S = reinterpret_cast<float*>(lds);
+  const int* gmap = reinterpret_cast<const int*>(lds + GROUP_OFF);
+  const int tid = threadIdx.x;
+  const int rq = tid >> 3, seg = tid & 7, flip = (rq & 1) << 5;
+  const int c0 = 32 * seg;
+  // the map entries beside the span; -1 (never a run's group) where nothing lies beside it
+  const int left = seg > 0 ? gmap[c0 - 1] : (n0 > 0 ? gmap[0] : -1);
+  const int right = seg < 7 ? gmap[c0 + 32] : gmap[BN - 1];
+  const uint32_t id0 = (uint32_t)(g.doc_offset + n0 + c0);  // < 2^31 (the entry checks)
+  const int4* map4 = reinterpret_cast<const int4*>(gmap + c0);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    if (grp == (p >> 1)) {
+#pragma unroll
+      for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int r = 16 * ii + 4 * (lane >> 4) + e;
+            const int c = (64 * wn + 16 * j + (lane & 15)) ^ ((e & 1) << 5);
+            S[r * 256 + c] = acc[4 * (p & 1) + ii][j][e];
+          }
+    }
+    lds_barrier();
+    const int q = m0 + 64 * p + rq;
+    if (q < g.M) {
+      unsigned long long* dst =
+          reinterpret_cast<unsigned long long*>(g.gmax) + (int64_t)q * g.n_groups;
+      const float4* row4 = reinterpret_cast<const float4*>(S + rq * 256 + (c0 ^ flip));
+      int cur = -1;
+      uint64_t best = 0ull;
+      bool shared = false;
+      auto fold = [&](bool sh) {
+#ifdef IRC_GROUP_DIAG  // diagnostic builds, wrong results, for timing the epilogue's parts:
+        // 1: the folds write nothing (a guarded store keeps the keys live); 2: every fold
+        // is a plain store
+        if (IRC_GROUP_DIAG == 1 ? best != 0x123456789abcdefull : cur < 0) return;
+        sh = false;
+#endif
+        if (cur >= 0) {
+          if (sh) atomicMax(dst + cur, (unsigned long long)best);
+          else dst[cur] = best;
+        }
+      };
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float4 s4 = row4[i];
+        const int4 m4 = map4[i];
+        const float sv[4] = {s4.x, s4.y, s4.z, s4.w};
+        const int mv[4] = {m4.x, m4.y, m4.z, m4.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int gi = mv[e];
+          if (gi != cur) {
+            fold(shared);
+            cur = gi;
+            best = 0ull;
+            shared = (4 * i + e == 0) && gi == left;
+          }
+          if (gi >= 0) {
+            const float sc = F8 != 0 ? sv[e] * g.score_scale : sv[e];
+            const uint64_t key = make_key(sc, id0 + (uint32_t)(4 * i + e));
+            best = key > best ? key : best;
+          }
+        }
+      }
+      fold(shared || cur == right);
+    }
+    lds_barrier();  // every reader is done with S before the next pass writes it
+  }
+}
+
 template <bool AK, bool BK_, typename TO, int EPI, int F8 = 0, bool LN = false>
 __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
   __shared__ __attribute__((aligned(1024))) char lds[LDS_BYTES];
@@ -937,10 +1069,11 @@ __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
     split = rest % gridDim.z;
     batch = rest / gridDim.z;
   }
-  // EPI_SCAN (and EPI_PICK): query tiles fastest, so the blocks of one doc tile run back
-  // to back on one XCD and read it from that XCD's L2 (C4: 2048 queries = 8 query tiles)
+  // EPI_SCAN (and EPI_PICK, EPI_GROUP): query tiles fastest, so the blocks of one doc tile
+  // run back to back on one XCD and read it from that XCD's L2 (C4: 2048 queries = 8 query
+  // tiles)
   int tm, tn;
-  if (EPI == EPI_SCAN || EPI == EPI_PICK) {
+  if (EPI == EPI_SCAN || EPI == EPI_PICK || EPI == EPI_GROUP) {
     tm = bid % tiles_m;
     tn = bid / tiles_m;
   } else {
@@ -962,6 +1095,10 @@ __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
     static_assert(AK && BK_ && F8 != 2, "the pick ranges live past two K-major buffers");
     if (!pick_ranges(g, lds, m0, n0)) return;  // no candidate in this tile
   }
+  if constexpr (EPI == EPI_GROUP) {
+    static_assert(AK && BK_ && F8 != 2, "the group map lives past two K-major buffers");
+    if (!group_map(g, lds, n0)) return;  // no column of this tile is in a group
+  }
   f32x4 acc[8][4];
   mainloop<AK, BK_, F8>(g, A, B, m0, n0, kbeg, nk, lds, buf_bytes(AK, BK_), 0, false, acc, grp,
                         wq, lane, nullptr, 0);
@@ -979,6 +1116,10 @@ __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
   }
   if constexpr (EPI == EPI_PICK) {
     epilogue_pick<F8>(g, acc, lds, m0, n0, grp, wn, lane);
+    return;
+  }
+  if constexpr (EPI == EPI_GROUP) {
+    epilogue_group<F8>(g, acc, lds, m0, n0, grp, wn, lane);
     return;
   }
 #ifdef IRC_PP_DIAG_NOEPI  // diagnostic build: main loop only (a guarded store of the sum of
@@ -1252,6 +1393,16 @@ void run_pick(const PArgs& a, hipStream_t st, bool fp8) {
                        dim3(NT), 0, st, a);
   else
     hipLaunchKernelGGL((gemm_pp_kernel<true, true, float, EPI_PICK>), dim3((unsigned)tiles),
+                       dim3(NT), 0, st, a);
+}
+
+void run_group(const PArgs& a, hipStream_t st, bool fp8) {
+  const int64_t tiles = ((int64_t)(a.M + 255) / 256) * ((a.N + 255) / 256);
+  if (fp8)
+    hipLaunchKernelGGL((gemm_pp_kernel<true, true, float, EPI_GROUP, 1>), dim3((unsigned)tiles),
+                       dim3(NT), 0, st, a);
+  else
+    hipLaunchKernelGGL((gemm_pp_kernel<true, true, float, EPI_GROUP>), dim3((unsigned)tiles),
                        dim3(NT), 0, st, a);
 }
 

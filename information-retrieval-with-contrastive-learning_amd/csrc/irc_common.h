@@ -245,6 +245,33 @@ __device__ __forceinline__ uint64_t make_key(float score, uint32_t gidx) {
   return ((uint64_t)orderable_f32(score) << 32) | (uint64_t)(uint32_t)(~gidx);
 }
 
+// The group of global row id: the g with group_off[g] <= id < group_off[g + 1] (upper
+// bound, so repeated offsets -- empty groups -- are stepped over), -1 for a row of no group.
+// The search starts from RC_NS samples of group_off the workgroup keeps in LDS -- s_first =
+// group_off[0], s_samp[t] = group_off[min((t + 1) * stride, n_groups)], so the last one is
+// group_off[n_groups] -- and only its last log2(stride) steps read global memory.
+constexpr int RC_NS = 256;
+__device__ __forceinline__ int group_of(const int64_t* __restrict__ group_off, int n_groups,
+                                        int64_t stride, int64_t s_first,
+                                        const int64_t* s_samp, int64_t id) {
+  if (n_groups <= 0 || id < s_first || id >= s_samp[RC_NS - 1]) return -1;
+  int c = 0, ch = RC_NS - 1;  // samples <= id: fewer than RC_NS, the last one is above id
+  while (c < ch) {
+    const int mid = (c + ch) >> 1;
+    if (s_samp[mid] <= id) c = mid + 1;
+    else ch = mid;
+  }
+  // group_off[c * stride] <= id < group_off[min((c + 1) * stride, n_groups)]
+  const int64_t top = (c + 1) * stride;
+  int lo = (int)(c * stride), hi = (int)(top < n_groups ? top : n_groups) - 1;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (group_off[mid + 1] <= id) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
 __device__ __forceinline__ float bf16_to_f32(unsigned short b) {
   return __uint_as_float(((uint32_t)b) << 16);
 }

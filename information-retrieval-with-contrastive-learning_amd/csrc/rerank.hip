@@ -44,6 +44,10 @@
 //    so merge_collapse_kernel sorts the query's P * kin entries by row id (a group is a run
 //    of the sorted ids), keeps the maximum key of every group, and the same select returns
 //    the top-k distinct groups.
+//  * irc_scan_topk_grouped is the grouped top-k with EVERY row of the shard a candidate of
+//    every query: no list, no scoring kernel of this file, no collapse -- the ping-pong GEMM
+//    loop's group epilogue (gemm_pp.hip, EPI_GROUP) writes one key per (query, group) and the
+//    same select ranks each query's n_groups keys.  Its own check sequence (no candidates).
 //
 // Layout: each thing exists once.  Device: score_chunk<E4M3, D> is the scoring body of both
 // gathered kernels (Operand<E4M3, D> holds what differs: piece type, pieces per lane, row
@@ -529,32 +533,8 @@ __global__ __launch_bounds__(RF_NT) void rerank_foreign_kernel(
     keys[i < pre ? c0 + i : lb + (i - pre)] = 0ull;
 }
 
-// The group of global row id: the g with group_off[g] <= id < group_off[g + 1] (upper
-// bound, so repeated offsets -- empty groups -- are stepped over), -1 for a row of no group.
-// The search starts from RC_NS samples of group_off the workgroup keeps in LDS -- s_first =
-// group_off[0], s_samp[t] = group_off[min((t + 1) * stride, n_groups)], so the last one is
-// group_off[n_groups] -- and only its last log2(stride) steps read global memory.
-constexpr int RC_NS = 256;
-__device__ __forceinline__ int group_of(const int64_t* __restrict__ group_off, int n_groups,
-                                        int64_t stride, int64_t s_first,
-                                        const int64_t* s_samp, int64_t id) {
-  if (n_groups <= 0 || id < s_first || id >= s_samp[RC_NS - 1]) return -1;
-  int c = 0, ch = RC_NS - 1;  // samples <= id: fewer than RC_NS, the last one is above id
-  while (c < ch) {
-    const int mid = (c + ch) >> 1;
-    if (s_samp[mid] <= id) c = mid + 1;
-    else ch = mid;
-  }
-  // group_off[c * stride] <= id < group_off[min((c + 1) * stride, n_groups)]
-  const int64_t top = (c + 1) * stride;
-  int lo = (int)(c * stride), hi = (int)(top < n_groups ? top : n_groups) - 1;
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (group_off[mid + 1] <= id) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
+// group_of (irc_common.h, shared with the scan's group epilogue in gemm_pp.hip): the group of
+// a global row id, searched from RC_NS samples of group_off the workgroup keeps in LDS.
 
 // Grouped top-k (irc_rerank_topk_grouped): between scoring and select, every key that is
 // not the maximum of its run becomes 0.  A run is a maximal stretch of consecutive
@@ -823,6 +803,27 @@ static bool merge_sizes_ok(int64_t P, int64_t Q, int64_t kin) {
          kin <= S_STAGE && P * kin <= S_STAGE;
 }
 
+// irc_scan_topk_grouped's workspace: gmax [Q][n_groups], the keys the select ranks, then its
+// Q + 1 list offsets q * n_groups
+static size_t scan_group_keys_bytes(int64_t Q, int64_t n_groups) {
+  return align256((size_t)(Q * n_groups) * 8);
+}
+static size_t scan_group_workspace_bytes(int64_t Q, int64_t n_groups) {
+  return scan_group_keys_bytes(Q, n_groups) + align256((size_t)(Q + 1) * 8);
+}
+// the sizes the workspace formula is defined for (the call itself reports them)
+static bool scan_group_sizes_ok(int64_t Q, int64_t n_groups) {
+  return Q >= 0 && Q < (1ll << 31) - 1 && n_groups >= 0 && n_groups < (1ll << 31) - 1 &&
+         Q * n_groups < (1ll << 31) * 256;
+}
+
+// list_off[q] = q * L for q <= Q: the select's offsets over Q lists of one length
+__global__ __launch_bounds__(256) void list_off_kernel(int64_t* __restrict__ list_off, int64_t Q,
+                                                       int64_t L) {
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (q <= Q) list_off[q] = q * L;
+}
+
 // keys, and for the grouped form rmax and head after them: 8 bytes per candidate each, every
 // region on a 256-byte boundary
 static size_t region_bytes(int64_t n_cand) {
@@ -1062,6 +1063,91 @@ extern "C" int irc_rerank_topk_grouped(const void* queries, const void* docs, in
                      (flags & IRC_RERANK_E4M3) != 0, true, group_off, n_groups},
                     queries, docs, Q, N, D, cand, cand_off, n_cand, k, doc_offset, score_scale,
                     workspace, workspace_bytes, out_score, out_idx, out_n, stream);
+}
+
+extern "C" int64_t irc_scan_topk_grouped_workspace(int64_t Q, int64_t n_groups, int64_t k) {
+  (void)k;
+  if (!scan_group_sizes_ok(Q, n_groups)) return 0;  // the call itself reports the sizes
+  return (int64_t)scan_group_workspace_bytes(Q, n_groups);
+}
+
+// The dense scan per group: every row of the shard is a candidate of every query, so there
+// is no list.  The group epilogue of the ping-pong GEMM loop (gemm_pp.hip, EPI_GROUP) folds
+// each score tile into gmax[q][g], one key per (query, group), and the select of rerank_run
+// ranks each query's n_groups keys (0: the group has no row in this shard).  The order of
+// the checks is part of the interface (tests/test_scan_group_cpu.py).
+extern "C" int irc_scan_topk_grouped(const void* queries, const void* docs, int64_t Q, int64_t N,
+                                     int64_t D, int64_t k, int64_t doc_offset,
+                                     const int64_t* group_off, int64_t n_groups, uint32_t flags,
+                                     float score_scale, void* workspace,
+                                     int64_t workspace_bytes, float* out_score,
+                                     int64_t* out_idx, int32_t* out_n, irc_stream_t stream) {
+  const char* name = "scan_topk_grouped";
+  const bool e4m3 = (flags & IRC_RERANK_E4M3) != 0;
+  IRC_REQUIRE(Q >= 0 && N >= 0, "%s: negative size", name);
+  IRC_REQUIRE(k >= 1 && k <= RR_MAXK, "%s: k=%lld outside [1, %d]", name, (long long)k, RR_MAXK);
+  IRC_REQUIRE(supported_d(D), "%s: unsupported D=%lld", name, (long long)D);
+  IRC_REQUIRE(!e4m3 || D % 128 == 0, "%s: unsupported D=%lld for e4m3 operands (D %% 128 == 0)",
+              name, (long long)D);
+  IRC_REQUIRE((flags & ~IRC_RERANK_E4M3) == 0, "%s: unsupported flags 0x%x (IRC_RERANK_E4M3 only)",
+              name, (unsigned)flags);
+  IRC_REQUIRE(!e4m3 || pow2_scale(score_scale), "%s: score_scale must be a power of two", name);
+  IRC_REQUIRE(doc_offset >= 0 && doc_offset + N < (1ll << 31),
+              "%s: global doc ids must fit int32 (doc_offset + N < 2^31)", name);
+  IRC_REQUIRE(Q < (1ll << 31) - 1, "%s: Q too large", name);
+  IRC_REQUIRE(n_groups >= 0 && n_groups < (1ll << 31) - 1,
+              "%s: n_groups=%lld outside [0, 2^31 - 1)", name, (long long)n_groups);
+  IRC_REQUIRE(Q * n_groups < (1ll << 31) * 256, "%s: Q x n_groups too large", name);
+  // one workgroup per (query tile, doc tile): the grid and the kernel's int tile count
+  IRC_REQUIRE(((Q + 255) / 256) * ((N + 255) / 256) < (1ll << 31), "%s: Q x N too large", name);
+  const int64_t need = (int64_t)scan_group_workspace_bytes(Q, n_groups);
+  if (workspace == nullptr || workspace_bytes < need) {
+    set_error("%s: workspace %lld < required %lld bytes", name, (long long)workspace_bytes,
+              (long long)need);
+    return IRC_E_WORKSPACE;
+  }
+  if (Q == 0) return IRC_OK;
+  IRC_REQUIRE(queries && group_off && out_score && out_idx && out_n && (N == 0 || docs),
+              "%s: null pointer", name);
+  IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
+              "%s: queries and docs must be 16-byte aligned", name);
+  hipStream_t st = as_stream(stream);
+  uint64_t* gmax = static_cast<uint64_t*>(workspace);
+  int64_t* list_off = reinterpret_cast<int64_t*>(static_cast<char*>(workspace) +
+                                                 scan_group_keys_bytes(Q, n_groups));
+  const int64_t n_keys = Q * n_groups;
+  prof_begin(st);
+  // key 0: no row of the group in this shard (the select skips zeros)
+  if (n_keys > 0 && hipMemsetAsync(gmax, 0, (size_t)n_keys * 8, st) != hipSuccess)
+    return check_launch("scan_group memset");
+  if (N > 0 && n_groups > 0) {
+    gpp::PArgs a{};
+    a.A = static_cast<const unsigned short*>(queries);
+    a.B = static_cast<const unsigned short*>(docs);
+    a.M = (int)Q;
+    a.N = (int)N;
+    a.K = (int)(e4m3 ? D / 2 : D);  // 2-byte units
+    a.kchunk = a.K;
+    a.lda = a.K;
+    a.ldb = a.K;
+    a.doc_offset = doc_offset;
+    if (e4m3) a.score_scale = score_scale;
+    a.gmax = gmax;
+    a.group_off = group_off;
+    a.n_groups = (int)n_groups;
+    gpp::run_group(a, st, e4m3);
+  }
+  // the bytes the pass streams: the shard once per query tile, and the zeroed keys
+  prof_end(e4m3 ? "scan_group_fp8_score" : "scan_group_score", st,
+           (double)((Q + 255) / 256) * (double)N * D * (e4m3 ? 1.0 : 2.0) + (double)n_keys * 8.0);
+  if (int rc = check_launch(e4m3 ? "scan_group_fp8_score" : "scan_group_score")) return rc;
+  hipLaunchKernelGGL(list_off_kernel, dim3((unsigned)(Q / 256 + 1)), dim3(256), 0, st, list_off, Q,
+                     n_groups);
+  prof_begin(st);
+  hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)Q), dim3(SNT), 0, st, gmax, list_off,
+                     n_keys, (int)k, out_score, out_idx, out_n);
+  prof_end("rerank_select", st, (double)n_keys * 8.0);
+  return check_launch("rerank_select_kernel");
 }
 
 extern "C" int64_t irc_topk_merge_grouped_workspace(int64_t P, int64_t Q, int64_t kin) {

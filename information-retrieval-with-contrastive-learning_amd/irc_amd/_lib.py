@@ -54,6 +54,9 @@ SIGNATURES = {
                                       P, I64, P, P, P, P]),
     "irc_topk_merge_grouped_workspace": (I64, [I64, I64, I64]),
     "irc_topk_merge_grouped": (I32, [P, P, I64, I64, I64, I64, P, I64, P, I64, P, P, P, P]),
+    "irc_scan_topk_grouped_workspace": (I64, [I64, I64, I64]),
+    "irc_scan_topk_grouped": (I32, [P, P, I64, I64, I64, I64, I64, P, I64, U32, F32, P, I64, P, P,
+                                    P, P]),
     "irc_scan_topk_fp8_workspace": (I64, [I64, I64, I64, I64]),
     "irc_scan_topk_fp8": (I32, [P, P, I64, I64, I64, I64, I64, F32, P, I64, P, P, P]),
     "irc_scan_scores_fp8": (I32, [P, P, I64, I64, I64, P, P]),

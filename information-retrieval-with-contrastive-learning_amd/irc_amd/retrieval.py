@@ -12,7 +12,9 @@ scans the local shard (global indices via the shard offset), all-gathers the
 per-shard top-k lists and merges them with the same exact rule.  The candidate-restricted
 top-k (``search_candidates``) is sharded the same way: the queries and their candidate lists
 are all-gathered, every shard ranks the candidates it owns, and the per-shard lists merge by
-``topk_merge``, or by ``topk_merge_grouped`` when the unit is a group of rows.
+``topk_merge``, or by ``topk_merge_grouped`` when the unit is a group of rows.  The scan has
+that unit too: ``search(..., group_off=)`` returns the top-k groups of the whole corpus
+(``scan_topk_grouped``), each shard over its own slice of the groups (``local_group_slice``).
 """
 from __future__ import annotations
 
@@ -317,6 +319,92 @@ def _check_group_off(group_off, queries):
         raise ValueError(f"group_off is on {group_off.device}, the queries on {queries.device}")
 
 
+def scan_topk_grouped(queries: torch.Tensor, docs: torch.Tensor, k: int, group_off,
+                      doc_offset: int = 0, ws_tag: str = "scan_group",
+                      max_workspace_bytes: int = 1 << 30):
+    """The dense scan per group of rows (irc_scan_topk_grouped): each query's top-k distinct
+    groups of the WHOLE shard, each by its best row -- what ``rerank_topk(method="stream",
+    group_off=...)`` returns when every row is a candidate of every query, bit for bit, with
+    no candidate list: the GEMM loop's epilogue folds each score tile into one key per (query,
+    group).
+
+    queries [Q, D], docs [N, D] (one shard, first global id ``doc_offset``), bf16 on one HIP
+    device; ``group_off`` int64 [n_groups + 1] on that device, non-decreasing, in GLOBAL row
+    ids, as for ``rerank_topk``: a group may begin before the shard or end past it (only its
+    rows here count; ``topk_merge_grouped`` joins the halves of two shards), and shard rows
+    outside [group_off[0], group_off[-1]) are never returned.  Returns (scores fp32 [Q, k],
+    idx int64 [Q, k] global row ids, n int32 [Q], groups int64 [Q, k]) as the grouped
+    ``rerank_topk`` does: by (score desc, row id asc), ties within a group to the lower id,
+    n[q] = min(k, groups with a row in the shard), padding (-inf, -1, group -1).  Exact.
+
+    The workspace holds 8 bytes per (query, group); when that exceeds
+    ``max_workspace_bytes`` the batch runs in chunks of a multiple of 256 queries (at least
+    256) and the results are concatenated -- the shard streams once per 256-query tile
+    anyway, so chunking reads no more."""
+    if group_off is None:
+        raise TypeError("group_off must be an int64 tensor, not None")
+    _check_group_off(group_off, queries)
+    require_hip(queries, docs, group_off)
+    q = contig(queries, torch.bfloat16)
+    d = contig(docs, torch.bfloat16)
+    if d.shape[1] != q.shape[1]:
+        raise ValueError(f"dim mismatch: queries D={q.shape[1]}, docs D={d.shape[1]}")
+    return _scan_group_call(q, d, k, group_off, doc_offset, 1.0, ws_tag, max_workspace_bytes)
+
+
+def scan_topk_grouped_fp8(queries: torch.Tensor, docs: torch.Tensor, k: int, group_off,
+                          doc_offset: int = 0, score_scale: float = 1.0,
+                          ws_tag: str = "scan_group", max_workspace_bytes: int = 1 << 30):
+    """``scan_topk_grouped`` over e4m3 operands: queries [Q, D] and docs [N, D] are uint8 codes
+    (``quantize_fp8``), D % 128 == 0.  The scores are the fp32 dot products of the decoded
+    values times ``score_scale`` (a power of two), as ``scan_topk_fp8`` reports them."""
+    if group_off is None:
+        raise TypeError("group_off must be an int64 tensor, not None")
+    _check_group_off(group_off, queries)
+    _require_e4m3(queries, docs)  # a wrong dtype is a TypeError on any device
+    q, d = _fp8_operands(queries, docs)
+    require_hip(group_off)
+    return _scan_group_call(q, d, k, group_off, doc_offset, float(score_scale), ws_tag,
+                            max_workspace_bytes)
+
+
+def _scan_group_call(q, d, k, group_off, doc_offset, score_scale, ws_tag, max_workspace_bytes):
+    """The part of ``scan_topk_grouped`` and ``scan_topk_grouped_fp8`` after their operand
+    checks: the query chunks, the outputs and the native call (uint8 operands: e4m3)."""
+    Q, D = q.shape
+    N = d.shape[0]
+    go = group_off.contiguous()
+    n_groups = go.numel() - 1
+    flags = RERANK_FLAG_E4M3 if q.dtype == torch.uint8 else 0
+    out_s = torch.empty((Q, k), dtype=torch.float32, device=q.device)
+    out_i = torch.empty((Q, k), dtype=torch.int64, device=q.device)
+    out_n = torch.empty((Q,), dtype=torch.int32, device=q.device)
+    chunk = max(Q, 1)
+    if Q * n_groups * 8 > max_workspace_bytes:
+        chunk = max(256, max_workspace_bytes // (8 * n_groups) // 256 * 256)
+    for lo in range(0, Q, chunk):
+        hi = min(Q, lo + chunk)
+        nbytes = int(_lib.fn("irc_scan_topk_grouped_workspace")(hi - lo, n_groups, k))
+        ws = workspace(nbytes, q.device, ws_tag)
+        _lib.call("irc_scan_topk_grouped", ptr(q[lo:hi]), ptr(d), hi - lo, N, D, k, doc_offset,
+                  ptr(go), n_groups, flags, score_scale, ptr(ws), ws.numel(),
+                  ptr(out_s[lo:hi]), ptr(out_i[lo:hi]), ptr(out_n[lo:hi]), stream_ptr(q.device))
+    return out_s, out_i, out_n, _groups_of(go, out_i)
+
+
+def local_group_slice(group_off: torch.Tensor, doc_offset: int, N: int):
+    """(g_lo, g_hi): the groups a shard of N rows from global id ``doc_offset`` can touch are
+    ``group_off[g_lo : g_hi + 1]`` -- g_lo the number of g with group_off[g + 1] <= doc_offset
+    (groups that end at or before the shard), g_hi the number of g with group_off[g] <
+    doc_offset + N (groups that begin before its end).  g_hi <= g_lo: the slice is empty.
+    Pure torch on the tensor's device (CPU tensors too); reading the two counts is one
+    synchronisation."""
+    go = group_off.reshape(-1).to(torch.int64)
+    both = torch.stack([(go[1:] <= doc_offset).sum(), (go[:-1] < doc_offset + N).sum()])
+    g_lo, g_hi = both.tolist()
+    return int(g_lo), int(g_hi)
+
+
 def rerank_topk(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
                 cand_off: torch.Tensor, k: int, doc_offset: int = 0, ws_tag: str = "rerank",
                 method: str = "gather", ascending: bool = False, group_off=None):
@@ -549,26 +637,87 @@ class ShardedDenseIndex:
 
     # The two device steps are methods so the collective orchestration can be
     # exercised on CPU (gloo) with a test double in tests/test_dist_cpu.py.
-    def _local_topk(self, queries, k, ws_tag="scan"):
+    def _local_topk(self, queries, k, ws_tag="scan", group_off=None):
+        """This shard's top-k: (scores, idx), or with ``group_off`` the top-k per group
+        (scores, idx, n) over the shard's own slice of the groups."""
+        if group_off is not None:
+            go = self._local_groups(group_off)
+            if self.dtype == "fp8":
+                q8 = quantize_fp8(queries, self.fp8_scale)
+                return scan_topk_grouped_fp8(q8, self.docs, k, go, self.doc_offset,
+                                             1.0 / (self.fp8_scale * self.fp8_scale),
+                                             ws_tag=ws_tag)[:3]
+            return scan_topk_grouped(queries, self.docs, k, go, self.doc_offset,
+                                     ws_tag=ws_tag)[:3]
         if self.dtype == "fp8":
             q8 = quantize_fp8(queries, self.fp8_scale)
             return scan_topk_fp8(q8, self.docs, k, self.doc_offset,
                                  1.0 / (self.fp8_scale * self.fp8_scale), ws_tag=ws_tag)
         return scan_topk(queries, self.docs, k, self.doc_offset, ws_tag=ws_tag)
 
+    def _local_groups(self, group_off):
+        """``group_off`` cut to the groups this shard can touch (``local_group_slice``; one
+        entry, no group, when it touches none), so the per-shard workspace is proportional to
+        the shard's own groups.  Computed once per ``group_off`` tensor OBJECT and kept on the
+        index: the same object passed again costs nothing, another one a host sync."""
+        memo = getattr(self, "_group_slice", None)
+        if memo is not None and memo[0] is group_off:
+            return memo[1]
+        g_lo, g_hi = local_group_slice(group_off, self.doc_offset, self.docs.shape[0])
+        cut = group_off[g_lo:g_hi + 1] if g_hi > g_lo else group_off[g_lo:g_lo + 1]
+        self._group_slice = (group_off, cut.contiguous())
+        return self._group_slice[1]
+
     def _merge(self, scores, idx, k):
         return topk_merge(scores, idx, k)
 
     def search(self, queries: torch.Tensor, k: int, equal_counts: bool = False,
-               ws_tag: str = "scan"):
+               ws_tag: str = "scan", group_off=None):
         """Global top-k of the gathered queries.  ``equal_counts``: every rank
         passes the same number of queries, so the ragged-count exchange (a host
-        sync) is skipped and the whole search stays stream-ordered."""
+        sync) is skipped and the whole search stays stream-ordered.
+
+        ``group_off`` (int64 [n_groups + 1], global row ids, non-decreasing, on the queries'
+        device): the top-k distinct GROUPS of the whole corpus, each by its best row, as
+        ``search_candidates(..., group_off=)`` ranks them when every row is a candidate --
+        (scores [Q, k], idx [Q, k] global row ids, n [Q], groups [Q, k]), by (score desc, row
+        id asc), padding (-inf, -1, group -1).  Each shard runs ``scan_topk_grouped`` over
+        its own slice of the groups (``local_group_slice``); the slice is computed once per
+        ``group_off`` tensor object -- memoised on the index and compared with ``is`` -- and
+        costs one host synchronisation on first use, so pass the same tensor again, not a
+        copy.  Over a process group the per-shard lists merge by ``topk_merge_grouped``
+        (k * world size <= 8192), which keeps one row of a group whose rows lie in two
+        shards; ``groups`` counts in the full ``group_off``.  fp8 indexes quantise the
+        queries and descale as without groups (D % 128 == 0, else ValueError).  As for
+        ``search_candidates``, every argument check runs on the rank's own arguments
+        BEFORE the first collective.  ``search_many`` has no grouped form."""
+        if group_off is None:
+            if not self._sharded():
+                return self._local_topk(queries, k, ws_tag)
+            allq = self._gather_queries(queries, equal_counts)  # (1)
+            s, i = self._local_topk(allq, k, ws_tag)  # (2)
+            return self._exchange_merge(s, i, k)  # (3)
+        _check_group_off(group_off, queries)
+        if self.dtype == "fp8" and self.docs.shape[1] % 128 != 0:
+            raise ValueError("fp8 index: the grouped scan needs D % 128 == 0, not "
+                             f"D={self.docs.shape[1]}")
+        if queries.dim() != 2 or queries.shape[1] != self.docs.shape[1]:
+            raise ValueError(f"dim mismatch: queries {tuple(queries.shape)}, docs "
+                             f"D={self.docs.shape[1]}")
+        if not 1 <= k <= 1024:
+            raise ValueError(f"k={k} outside [1, 1024]")
         if not self._sharded():
-            return self._local_topk(queries, k, ws_tag)
+            s, i, n = self._local_topk(queries, k, ws_tag, group_off)
+            return s, i, n, _groups_of(group_off, i)
+        import torch.distributed as dist
+
+        world = dist.get_world_size(self.group)
+        if k * world > 8192:
+            raise ValueError(f"k * world size = {k} x {world} above the grouped merge's 8192 "
+                             "entries per query")
         allq = self._gather_queries(queries, equal_counts)  # (1)
-        s, i = self._local_topk(allq, k, ws_tag)  # (2)
-        return self._exchange_merge(s, i, k)  # (3)
+        s, i, _ = self._local_topk(allq, k, ws_tag, group_off)  # (2)
+        return self._exchange_merge(s, i, k, group_off)  # (3)
 
     def search_candidates(self, queries: torch.Tensor, cand: torch.Tensor,
                           cand_off: torch.Tensor, k: int, ws_tag: str = "rerank",
@@ -779,9 +928,11 @@ class ShardedDenseIndex:
         dist.all_gather(gathered, qpad, group=self.group)
         return torch.cat([g[:c] for g, c in zip(gathered, counts)], dim=0)
 
-    def _exchange_merge(self, s, i, k):
+    def _exchange_merge(self, s, i, k, group_off=None):
         """(3) every shard's exact top-k lists (global doc ids) all-gathered and merged
-        by the (score desc, index asc) rule: every rank gets the global result."""
+        by the (score desc, index asc) rule: every rank gets the global result.  With
+        ``group_off`` the lists hold one row per group and merge per group
+        (``_merge_grouped``, as ``_exchange_merge_candidates`` does)."""
         import torch.distributed as dist
 
         world = dist.get_world_size(self.group)
@@ -789,6 +940,8 @@ class ShardedDenseIndex:
         ii = [torch.empty_like(i) for _ in range(world)]
         dist.all_gather(ss, s.contiguous(), group=self.group)
         dist.all_gather(ii, i.contiguous(), group=self.group)
+        if group_off is not None:
+            return self._merge_grouped(torch.stack(ss), torch.stack(ii), k, group_off)
         return self._merge(torch.stack(ss), torch.stack(ii), k)
 
     def search_many(self, batches, k: int, depth: int = 3, equal_counts: bool = False,

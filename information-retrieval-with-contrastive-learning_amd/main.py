@@ -19,8 +19,8 @@ gradient all-reduce; logging and checkpoints on rank 0) and ``--retrieval dense`
 the reference's sparse candidate filter per claim (default) or, with
 ``--retrieval dense``, the bi-encoder's exact top-k over the evidence corpus, or, with
 ``--retrieval hybrid``, that top-k over each claim's filter candidates only (the
-reference's two stages joined; ``--rerank-unit page`` ranks the k best
-pages, each by its best line, instead of the k best lines).  The compute runs on the
+reference's two stages joined).  With either of the two, ``--rerank-unit page`` ranks the
+k best pages, each by its best line, instead of the k best lines.  The compute runs on the
 MI355X HIP kernels only:
 ``--gpu -1`` (CPU) is rejected -- there is no CPU fallback in this build.
 """
@@ -72,11 +72,11 @@ def get_args(argv=None):
                         "the candidates only; scores may differ in the last bits (another "
                         "fp32 summation order)")
     p.add_argument("--rerank-unit", default="line", type=str, choices=["line", "page"],
-                   help="--retrieval hybrid: what the top-k counts. line (default): the k "
-                        "best evidence lines, several of which may be of one page. page: the "
-                        "k best pages, each by its best line (ties: the earlier line), "
-                        "collapsed on the device before the select; the printed recall is "
-                        "then over k pages")
+                   help="--retrieval dense / hybrid: what the top-k counts. line (default): "
+                        "the k best evidence lines, several of which may be of one page. "
+                        "page: the k best pages, each by its best line (ties: the earlier "
+                        "line), collapsed on the device before the select (dense: in the "
+                        "scan's GEMM epilogue); the printed recall is then over k pages")
     p.add_argument("--index-dtype", default="bf16", type=str, choices=["bf16", "fp8"],
                    help="--retrieval dense / hybrid: how the evidence corpus is kept in HBM. "
                         "bf16 (default), or fp8: e4m3 bytes at half the size, the claims "

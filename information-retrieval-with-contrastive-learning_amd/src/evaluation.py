@@ -108,7 +108,12 @@ def predict_dense(args, k=100):
     slice (irc_amd.retrieval.shard_bounds) in HBM, each claim batch is split over
     the ranks, and ShardedDenseIndex.search all-gathers the claim embeddings,
     scans every shard and merges the per-shard top-k -- every rank receives the
-    global result for the whole batch."""
+    global result for the whole batch.
+
+    ``args.rerank_unit == "page"`` (main.py --rerank-unit): the k best PAGES, each by its
+    best line, instead of the k best lines -- ``search(..., group_off=row_off)``, the page
+    -> row range map built while the lines are enumerated -- and the recall printed is
+    over k pages, as the FEVER labels count."""
     from irc_amd.retrieval import shard_bounds
 
     assert args.ckpt is not None
@@ -118,13 +123,17 @@ def predict_dense(args, k=100):
     group = getattr(args, "dist_group", None)
     world = int(getattr(args, "world_size", 1)) if group is not None else 1
     rank = int(getattr(args, "rank", 0)) if group is not None else 0
-    # evidence corpus = every evidence document line of the dev set's wiki pages
-    titles, texts = [], []
+    # evidence corpus = every evidence document line of the dev set's wiki pages; row_off:
+    # page p owns the rows [row_off[p], row_off[p + 1])
+    titles, texts, row_off = [], [], [0]
     for title, page in loader.dataset.wiki.items():
         for line in page["lines"]:
             if line.strip():
                 titles.append(title)
                 texts.append(line)
+        row_off.append(len(texts))
+    by_page = getattr(args, "rerank_unit", "line") == "page"
+    row_off = torch.tensor(row_off, dtype=torch.int64, device=args.device) if by_page else None
     lo, hi = shard_bounds(len(texts), world, rank)
     index = ShardedDenseIndex(encode_corpus(model, texts[lo:hi], args.device), doc_offset=lo,
                               group=group, dtype=getattr(args, "index_dtype", "bf16"))
@@ -137,7 +146,8 @@ def predict_dense(args, k=100):
         mine = claims[c0:c1]
         q = model.ctx2vec(mine, args.device) if mine else \
             torch.empty((0, dim), dtype=torch.float32, device=args.device)
-        scores, idx = index.search(q, k)  # rows: the whole batch, in order
+        # rows: the whole batch, in order
+        idx = index.search(q, k, group_off=row_off)[1] if by_page else index.search(q, k)[1]
         torch.cuda.synchronize()
         if rank == 0:
             print(f"batch of {len(claims)} claims: {time.time() - s:.4f}s")
@@ -147,7 +157,7 @@ def predict_dense(args, k=100):
             hits += int(any(titles[j] in gold for j in row if j >= 0))
             total += 1
     if rank == 0:
-        print(f"evidence recall@{k}: {hits / max(total, 1):.4f}")
+        print(f"evidence recall@{k}{' (pages)' if by_page else ''}: {hits / max(total, 1):.4f}")
     return hits / max(total, 1)
 
 

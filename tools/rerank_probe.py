@@ -39,6 +39,11 @@ lists of kin = kout entries each, P x kin in (2, 100), (8, 100), (8, 1024) -- th
 of topk_merge (irc_topk_merge) and of topk_merge_grouped (irc_topk_merge_grouped) on the
 same lists, alternating window by window, and the grouped merge's two kernels from a
 profiled pass.  What the merge adds to a sharded search_candidates.
+``--scan-grouped [--dtype fp8]``: the dense scan per page, ShardedDenseIndex.search(group_off=
+...), on the same shard and page draw at Q in {1, 16, 64, 256}, alternating with search (the k
+best lines) and with the candidate route to the same pages, search_candidates(method="stream",
+group_off=...) over lists of ALL rows; profiles/scan_group_probe.json holds the bf16 and the
+fp8 run's lines under "bf16" and "fp8" (``--tables`` prints both).
 Prints a table to stderr and ONE JSON line to stdout."""
 import argparse
 import ctypes
@@ -288,6 +293,109 @@ def grouped_probe(args):
                       "cells": cells}))
 
 
+def scan_group_tables(r):
+    """The table of DESIGN.md 6e "Dense scan per group": per Q the line scan (a), the grouped
+    scan (b) and the candidate route over all-rows lists (c), and (b)'s two spans."""
+    print(f"{r['dtype']}: {r['n_groups']:,} groups over {r['N']:,} rows "
+          f"(mean {r['N'] / r['n_groups']:.1f}, longest {r['max_group_rows']}), k = {r['k']}\n")
+    print("| Q | (a) search, lines | (b) search, pages | (b) / (a) | (c) candidates, all rows | "
+          "(c) / (b) | (b) memset + GEMM + group epilogue | share of (b) | (b) select |\n"
+          "|---|---|---|---|---|---|---|---|---|")
+    for c in r["cells"]:
+        print(f"| {c['Q']} | {c['lines_call_us']:,.1f} | {c['pages_call_us']:,.1f} | "
+              f"{c['pages_over_lines']:.2f} | {c['route_call_us']:,.1f} | "
+              f"{c['route_over_pages']:.2f} | {c['group_span_us']:,.1f} | "
+              f"{100 * c['group_span_share']:.0f}% | {c['select_kernel_us']:,.1f} |")
+    print()
+    worst = max(r["cells"], key=lambda c: max(c["spread_pct"].values()))
+    print(f"largest min-max spread of a cell's windows: {max(worst['spread_pct'].values()):.2f}% "
+          f"(Q = {worst['Q']}); rounds per cell: {r['rounds']}")
+
+
+def scan_group_probe(args):
+    """--scan-grouped: on the probe's shard and its fixed-seed page draw (mean about 10
+    rows), per Q three calls of one ShardedDenseIndex alternating window by window: (a)
+    search (the k best lines), (b) search(group_off=...) (the k best pages, the GEMM loop's
+    group epilogue), (c) the route to (b)'s answer without it: search_candidates(method=
+    "stream", ascending=True, group_off=...) over lists of ALL rows.  Then a profiled pass of
+    (b): the span of the memset and the GEMM launch with the group epilogue -- launch events
+    cannot time the epilogue apart from the main loop of its own kernel -- and the select.
+    ONE JSON line to stdout."""
+    from irc_amd import _lib, retrieval
+
+    fp8 = args.dtype == "fp8"
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(2025)
+    docs = torch.nn.functional.normalize(
+        torch.randn(args.n, args.d, generator=g)).bfloat16().to(dev)
+    torch.manual_seed(2025)
+    index = retrieval.ShardedDenseIndex(docs, dtype=args.dtype)
+    del docs
+    # page sizes: 1 + an exponential draw of mean 9.5, rounded down -- the draw of --grouped
+    sizes = 1 + torch.empty(args.n, dtype=torch.float64).exponential_(1 / 9.5, generator=g).long()
+    ends = torch.cumsum(sizes, 0)
+    ends = ends[: int((ends < args.n).sum())]
+    group_off = torch.cat([torch.zeros(1, dtype=torch.int64), ends,
+                           torch.tensor([args.n])]).to(dev)
+    max_rows = int((group_off[1:] - group_off[:-1]).max())
+    span = b"scan_group_fp8_score" if fp8 else b"scan_group_score"
+    cells = []
+    for Q in args.q:
+        qq = torch.nn.functional.normalize(
+            torch.randn(Q, args.d, generator=g)).bfloat16().to(dev)
+        cand = torch.arange(args.n, dtype=torch.int32, device=dev).repeat(Q)
+        off = torch.arange(Q + 1, device=dev, dtype=torch.int64) * args.n
+        timed = [
+            ("lines", lambda: index.search(qq, args.k)),
+            ("pages", lambda: index.search(qq, args.k, group_off=group_off)),
+            ("route", lambda: index.search_candidates(qq, cand, off, args.k, method="stream",
+                                                      ascending=True, group_off=group_off)),
+        ]
+        same = all(torch.equal(x, y) for x, y in zip(timed[1][1](), timed[2][1]()))
+        est = {}
+        for name, fn in timed:
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            est[name] = _window_ms(fn, 5)
+        reps = {m: max(4, min(4000, int(args.window_ms / max(est[m], 1e-3)))) for m in est}
+        t = {m: [] for m, _ in timed}
+        for _ in range(args.rounds):  # alternate them window by window
+            for m, fn in timed:
+                t[m].append(_window_ms(fn, reps[m]))
+        lib.irc_prof_reset()
+        lib.irc_prof_enable(1)
+        for _ in range(min(reps["pages"], 48)):
+            timed[1][1]()
+        torch.cuda.synchronize()
+        lib.irc_prof_enable(0)
+        span_us, _ = _prof(lib, span)
+        select_us, _ = _prof(lib, b"rerank_select")
+        med = {m: statistics.median(t[m]) * 1e3 for m in t}
+        cell = {"Q": Q, "group_span_us": span_us, "select_kernel_us": select_us,
+                "group_span_share": span_us / med["pages"],
+                "pages_over_lines": med["pages"] / med["lines"],
+                "route_over_pages": med["route"] / med["pages"],
+                "route_equals_pages_bitwise": bool(same), "reps": reps,
+                "spread_pct": {m: 100.0 * (max(t[m]) - min(t[m])) / statistics.median(t[m])
+                               for m in t}}
+        for m in t:
+            cell[f"{m}_call_us"] = med[m]
+            cell[f"{m}_call_us_minmax"] = [min(t[m]) * 1e3, max(t[m]) * 1e3]
+        cells.append(cell)
+        print(f"Q={Q:4d}  lines {med['lines']:9.1f} us  pages {med['pages']:9.1f} us "
+              f"({cell['pages_over_lines']:.2f})  all-rows route {med['route']:10.1f} us "
+              f"({cell['route_over_pages']:.2f} x pages)  group span {span_us:8.1f} us  select "
+              f"{select_us:7.1f} us  same bits {same}", file=sys.stderr, flush=True)
+        del cand, off
+    print(json.dumps({"probe": "scan_grouped", "device": torch.cuda.get_device_name(0),
+                      "dtype": args.dtype, "N": args.n, "D": args.d, "k": args.k,
+                      "rounds": args.rounds, "window_ms": args.window_ms,
+                      "n_groups": int(group_off.numel() - 1), "max_group_rows": max_rows,
+                      "cells": cells}))
+
+
 def merge_tables(r):
     """The table of DESIGN.md 6e "Across shards": per shape the two merges' call times and
     the grouped merge's kernels."""
@@ -399,10 +507,14 @@ def main():
             return merge_tables(rec)
         if isinstance(rec, dict) and rec.get("probe") == "rerank_grouped":
             return grouped_tables(rec)
-        if isinstance(rec, dict) and "bf16" in rec and "fp8" in rec:  # the two grouped runs
-            grouped_tables(rec["bf16"])
+        if isinstance(rec, dict) and rec.get("probe") == "scan_grouped":
+            return scan_group_tables(rec)
+        if isinstance(rec, dict) and "bf16" in rec and "fp8" in rec:  # the two runs of a probe
+            show = scan_group_tables if rec["bf16"].get("probe") == "scan_grouped" else \
+                grouped_tables
+            show(rec["bf16"])
             print()
-            return grouped_tables(rec["fp8"])
+            return show(rec["fp8"])
         return tables(sys.argv[2])
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=250_000)
@@ -420,12 +532,17 @@ def main():
                     help="time rerank_topk(group_off=...) next to the ungrouped call")
     ap.add_argument("--merge", action="store_true",
                     help="time topk_merge and topk_merge_grouped on the same per-shard lists")
+    ap.add_argument("--scan-grouped", action="store_true",
+                    help="time search(group_off=...) next to search and to the candidate "
+                         "route over all-rows lists")
     args = ap.parse_args()
     fp8 = args.dtype == "fp8"
     if not torch.cuda.is_available():
         raise SystemExit("rerank_probe measures on a HIP device; none is visible")
     if args.merge:
         return merge_probe(args)
+    if args.scan_grouped:
+        return scan_group_probe(args)
     if args.grouped:
         return grouped_probe(args)
     from irc_amd import _lib, retrieval
