@@ -266,6 +266,54 @@ int irc_scan_topk_grouped(const void* queries, const void* docs, int64_t Q, int6
                           float score_scale, void* workspace, int64_t workspace_bytes,
                           float* out_score, int64_t* out_idx, int32_t* out_n, irc_stream_t stream);
 
+/* Cluster-pruned dense top-k (an inverted-file index): the dense scoring of
+ * src/evaluation.py:110-112 restricted to the rows of the lists each query probes.  faiss
+ * appears in the reference only as the clustering of src/contrastor/utils.py:39-47; the index
+ * built on a clustering is this project's.
+ *
+ * docs [N, D] bf16 is the shard IN LIST ORDER: list c owns the rows [list_off[c],
+ * list_off[c + 1]) (list_off [nlist + 1] int64, non-decreasing, list_off[nlist] <= N; empty
+ * lists allowed) and row_id [N] int32 holds each row's GLOBAL id, which is what out_idx and the
+ * tie rule use -- never the permuted position -- so per-shard results merge with
+ * irc_topk_merge as scan shards do.  probe [Q, nprobe] int32: the lists of each query, unique
+ * within a row, -1 = no list.  The other arrays are the plan of one search, built on the device
+ * from probe and list_off (retrieval.ivf_plan):
+ *   slot_off [Q * nprobe + 1] int64: pair (q, j) owns the keys [slot_off[q * nprobe + j], + rows
+ *     of its list); slot_off[Q * nprobe] <= total_rows;
+ *   cand_off [Q + 1] int64 = slot_off[q * nprobe];
+ *   pair_order [Q * nprobe] int32: the valid pairs, stable-sorted by list (the rest after them);
+ *   seg_off [nlist + 1] int64: list c's pairs are pair_order[seg_off[c] .. seg_off[c + 1]);
+ *   chunk_off [nlist + 1] int64: cumulative count of 32-pair chunks per list.
+ * A work item is (list, chunk of <= 32 pairs, segment of irc_ivf_tile_rows() rows): the segment
+ * streams once through the MFMA against the chunk's queries and every (pair, row) writes its
+ * one key; max_list_rows (>= the longest list) bounds the segments of the grid.  A plan that
+ * breaks these contracts may be ranked wrongly; nothing is read at or past row N or written
+ * outside the total_rows keys.
+ *
+ * Per query the output is the exact top-k over the union of its probed lists' rows by (score
+ * desc, global id asc), irc_scan_topk's rule; slots past out_n[q] = min(k, rows in the probed
+ * lists) are (-inf, -1).  The fp32 sum of a (query, row) has one fixed order, whatever else the
+ * call holds: the same bits with other queries in the batch, other lists probed, another
+ * place of the list.  Workspace (irc_ivf_topk_workspace): one 64-bit key per (pair, row),
+ * align256(total_rows * 8) + 256 bytes, every key written by the call (contents before it do
+ * not matter).
+ *
+ * Validation, in this order, each IRC_E_INVALID with a message that starts "ivf_topk:" and
+ * found before any device work: no negative size; 1 <= k <= 1024; D as irc_scan_topk accepts;
+ * 1 <= nprobe <= nlist; N < 2^31; Q * nprobe < 2^30; max_list_rows <= N and <= 65535
+ * segments; then the workspace (IRC_E_WORKSPACE, required and given sizes in the message).
+ * Q == 0 returns IRC_OK there and touches nothing; else no null array (docs may be null when
+ * N == 0) and queries / docs 16-byte aligned. */
+int irc_ivf_tile_rows(void);
+int64_t irc_ivf_topk_workspace(int64_t Q, int64_t nprobe, int64_t total_rows, int64_t k);
+int irc_ivf_topk(const void* queries, const void* docs, const int32_t* row_id,
+                 const int64_t* list_off, int64_t nlist, const int32_t* probe,
+                 const int64_t* slot_off, const int64_t* cand_off, const int32_t* pair_order,
+                 const int64_t* seg_off, const int64_t* chunk_off, int64_t Q, int64_t nprobe,
+                 int64_t N, int64_t D, int64_t k, int64_t total_rows, int64_t max_list_rows,
+                 void* workspace, int64_t workspace_bytes, float* out_score, int64_t* out_idx,
+                 int32_t* out_n, irc_stream_t stream);
+
 /* Raw score tile for tests / diagnostics: out[Q, N] fp32 = queries . docs^T
  * using the same MFMA path as irc_scan_topk. */
 int irc_scan_scores(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,

@@ -56,19 +56,21 @@
 // which holds the argument checks (their order is part of the interface), then runs
 // score_gather (the D switch) or score_stream (the pick GEMM's arguments), the collapse if
 // grouped, and the select.  A new operand type is one more Operand; a new entry one more Form.
+// The select has one launch site, select_topk (rerank_select.h), which the cluster-pruned
+// search (ivf.hip) ends in too.
 #include <stdint.h>
 
 #include <cmath>
 
 #include "gemm_pp.h"
 #include "irc_common.h"
+#include "rerank_select.h"
 
 namespace irc {
 namespace rerank {
 
 constexpr int RR_CHUNK = 256;  // candidates per scoring workgroup (= its threads)
 constexpr int RR_LPR = 8;      // lanes sharing one row
-constexpr int RR_MAXK = 1024;
 constexpr int SNT = 1024;      // select: threads per query
 constexpr int S_STAGE = 8192;  // keys staged in LDS (64 KB)
 constexpr int S_U = 16;        // key loads in flight per thread
@@ -496,6 +498,17 @@ __global__ __launch_bounds__(SNT) void rerank_select_kernel(
     out_idx[q * k + j] = id;
   }
   if (tid == 0) out_n[q] = cnt;
+}
+
+// The one launch site of the select (rerank_select.h): every pass that fills a key workspace
+// ends here, those of other files too.
+int select_topk(const uint64_t* keys, const int64_t* off, int64_t n_keys, int64_t Q, int k,
+                float* out_score, int64_t* out_idx, int32_t* out_n, hipStream_t st) {
+  prof_begin(st);
+  hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)Q), dim3(SNT), 0, st, keys, off, n_keys,
+                     k, out_score, out_idx, out_n);
+  prof_end("rerank_select", st, (double)n_keys * 8.0);
+  return check_launch("rerank_select_kernel");
 }
 
 // Stream method: keys of the candidates of other shards.  With ascending lists the ids
@@ -999,11 +1012,7 @@ static int rerank_run(const Form& f, const void* queries, const void* docs, int6
     prof_end("rerank_collapse", st, (double)n_cand * 44.0);
     if (int rc = check_launch("rerank_collapse_kernel")) return rc;
   }
-  prof_begin(st);
-  hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)Q), dim3(SNT), 0, st, keys, cand_off,
-                     n_cand, (int)k, out_score, out_idx, out_n);
-  prof_end("rerank_select", st, (double)n_cand * 8.0);
-  return check_launch("rerank_select_kernel");
+  return select_topk(keys, cand_off, n_cand, Q, (int)k, out_score, out_idx, out_n, st);
 }
 
 extern "C" int irc_rerank_topk(const void* queries, const void* docs, int64_t Q, int64_t N,
@@ -1143,11 +1152,7 @@ extern "C" int irc_scan_topk_grouped(const void* queries, const void* docs, int6
   if (int rc = check_launch(e4m3 ? "scan_group_fp8_score" : "scan_group_score")) return rc;
   hipLaunchKernelGGL(list_off_kernel, dim3((unsigned)(Q / 256 + 1)), dim3(256), 0, st, list_off, Q,
                      n_groups);
-  prof_begin(st);
-  hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)Q), dim3(SNT), 0, st, gmax, list_off,
-                     n_keys, (int)k, out_score, out_idx, out_n);
-  prof_end("rerank_select", st, (double)n_keys * 8.0);
-  return check_launch("rerank_select_kernel");
+  return select_topk(gmax, list_off, n_keys, Q, (int)k, out_score, out_idx, out_n, st);
 }
 
 extern "C" int64_t irc_topk_merge_grouped_workspace(int64_t P, int64_t Q, int64_t kin) {
@@ -1194,9 +1199,5 @@ extern "C" int irc_topk_merge_grouped(const float* in_score, const int64_t* in_i
   // per entry: score + id read, key written
   prof_end("topk_merge_collapse", st, (double)(Q * L) * 20.0);
   if (int rc = check_launch("merge_collapse_kernel")) return rc;
-  prof_begin(st);
-  hipLaunchKernelGGL(rerank_select_kernel, dim3((unsigned)Q), dim3(SNT), 0, st, keys, list_off,
-                     Q * L, (int)kout, out_score, out_idx, out_n);
-  prof_end("rerank_select", st, (double)(Q * L) * 8.0);
-  return check_launch("rerank_select_kernel");
+  return select_topk(keys, list_off, Q * L, Q, (int)kout, out_score, out_idx, out_n, st);
 }

@@ -15,6 +15,10 @@ are all-gathered, every shard ranks the candidates it owns, and the per-shard li
 ``topk_merge``, or by ``topk_merge_grouped`` when the unit is a group of rows.  The scan has
 that unit too: ``search(..., group_off=)`` returns the top-k groups of the whole corpus
 (``scan_topk_grouped``), each shard over its own slice of the groups (``local_group_slice``).
+
+Cluster-pruned search: ``IVFDenseIndex`` keeps a shard clustered into lists and a search ranks,
+exactly, only the rows of the lists nearest to each query (``ivf_topk``); sharded as the scan is,
+each shard probing its own lists.
 """
 from __future__ import annotations
 
@@ -226,6 +230,10 @@ def __getattr__(name):
     # (irc_rerank_stream_tile(), gpp::PICK_TILE in csrc/gemm_pp.h), read the same way.
     if name == "RERANK_STREAM_TILE":
         return int(_lib.load().irc_rerank_stream_tile())
+    # IVF_TILE_ROWS: the rows of one work item's segment in irc_ivf_topk (irc_ivf_tile_rows(),
+    # IVF_TILE_ROWS in csrc/ivf.hip); the list lengths around it are that kernel's edge cases.
+    if name == "IVF_TILE_ROWS":
+        return int(_lib.load().irc_ivf_tile_rows())
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -550,6 +558,101 @@ def expand_ranges(cand: torch.Tensor, cand_off: torch.Tensor, row_off: torch.Ten
                                     output_size=total)
     rows = start[owner] + (torch.arange(total, device=c.device) - (ends - length)[owner])
     return rows, rows_off
+
+
+IVF_CHUNK = 32  # queries one pass over a probed list serves: the MFMA's columns (csrc/ivf.hip)
+
+
+def ivf_layout(assign: torch.Tensor, nlist: int):
+    """The list order of a clustered corpus: (order int64 [N], list_off int64 [nlist + 1]).
+    ``order`` is the stable sort of the rows by their list ``assign`` (values in [0, nlist)),
+    so original ids ascend inside a list; list c is ``order[list_off[c]:list_off[c + 1]]``.
+    Empty lists are allowed.  Pure torch on the tensor's device (CPU tensors too)."""
+    a = assign.reshape(-1).to(torch.int64)
+    sa, order = torch.sort(a, stable=True)
+    list_off = torch.searchsorted(sa, torch.arange(nlist + 1, dtype=torch.int64, device=a.device))
+    return order, list_off
+
+
+def ivf_plan(probe: torch.Tensor, list_off: torch.Tensor):
+    """The index plumbing of one ``ivf_topk`` call, from ``probe`` (int32 [Q, nprobe]: list ids,
+    unique within a row, -1 = no list, skipped) and ``list_off``.  Pure torch on the tensors'
+    device (CPU tensors too), no host synchronisation.  Returns a dict of
+
+    * ``slot_off`` int64 [Q * nprobe + 1]: pair (q, j) owns the keys
+      ``[slot_off[q * nprobe + j], + len(list))``;
+    * ``cand_off`` int64 [Q + 1] = ``slot_off[::nprobe]``: a query's keys are one stretch;
+    * ``pair_order`` int32 [Q * nprobe]: the valid pairs, stable-sorted by list id (the -1
+      pairs fill the tail past ``seg_off[-1]``, so the length is known without a sync);
+    * ``seg_off`` int64 [nlist + 1]: list c's pairs are ``pair_order[seg_off[c]:seg_off[c + 1]]``;
+    * ``chunk_off`` int64 [nlist + 1]: the cumulative count of chunks of ``IVF_CHUNK`` pairs per
+      list -- one chunk's queries share one pass over the list."""
+    Q, nprobe = probe.shape
+    lo = list_off.reshape(-1).to(torch.int64)
+    nlist = lo.numel() - 1
+    dev = probe.device
+    flat = probe.reshape(-1).to(torch.int64)
+    valid = (flat >= 0) & (flat < nlist)  # an id that names no list owns no keys either
+    lens = lo[1:] - lo[:-1]
+    plen = torch.where(valid, lens[flat.clamp(0, max(nlist - 1, 0))], lens.new_zeros(()))
+    zero = torch.zeros(1, dtype=torch.int64, device=dev)
+    slot_off = torch.cat([zero, torch.cumsum(plen, 0)])
+    cand_off = slot_off[::nprobe].contiguous()
+    key = torch.where(valid, flat, flat.new_full((), nlist))
+    skey, pair_order = torch.sort(key, stable=True)
+    seg_off = torch.searchsorted(skey, torch.arange(nlist + 1, dtype=torch.int64, device=dev))
+    chunks = (seg_off[1:] - seg_off[:-1] + (IVF_CHUNK - 1)) // IVF_CHUNK
+    chunk_off = torch.cat([zero, torch.cumsum(chunks, 0)])
+    return {"slot_off": slot_off, "cand_off": cand_off, "pair_order": pair_order.to(torch.int32),
+            "seg_off": seg_off, "chunk_off": chunk_off}
+
+
+def ivf_topk(queries: torch.Tensor, docs: torch.Tensor, row_id: torch.Tensor,
+             list_off: torch.Tensor, probe: torch.Tensor, k: int, max_list_rows: int,
+             ws_tag: str = "ivf", total_rows=None):
+    """Exact top-k of each query over the rows of the lists it probes (irc_ivf_topk).
+
+    queries [Q, D] bf16; ``docs`` [N, D] bf16 IN LIST ORDER (``ivf_layout``), ``row_id`` int32
+    [N] the global id of each row, ``list_off`` int64 [nlist + 1]; ``probe`` int32 [Q, nprobe]
+    (``ivf_plan``); all on one HIP device.  ``max_list_rows`` is a host int, the longest list
+    (it bounds the grid).  Returns (scores fp32 [Q, k], idx int64 [Q, k] global ids, n int32
+    [Q]) by (score desc, global id asc); slots past n[q] = min(k, rows in the probed lists) are
+    (-inf, -1).  Each probed list is read once per 32 of the queries that probe it and scored
+    on MFMA; the fp32 sum of a (query, row) has one fixed order whatever else the call holds.
+
+    The workspace holds one key per (pair, row).  Their total is read from the plan with ONE
+    host synchronisation, as ``expand_ranges`` reads its row count, unless the caller passes
+    ``total_rows`` (an upper bound), which keeps the call stream-ordered."""
+    require_hip(queries, docs, row_id, list_off, probe)
+    q = contig(queries, torch.bfloat16)
+    d = contig(docs, torch.bfloat16)
+    if d.shape[1] != q.shape[1]:
+        raise ValueError(f"dim mismatch: queries D={q.shape[1]}, docs D={d.shape[1]}")
+    if probe.dim() != 2 or probe.shape[0] != q.shape[0]:
+        raise ValueError(f"probe must be [Q, nprobe] for {q.shape[0]} queries, not "
+                         f"{tuple(probe.shape)}")
+    if row_id.numel() != d.shape[0]:
+        raise ValueError(f"row_id has {row_id.numel()} entries for {d.shape[0]} rows")
+    Q, D = q.shape
+    N = d.shape[0]
+    nprobe = probe.shape[1]
+    pr = contig(probe, torch.int32)
+    rid = contig(row_id, torch.int32)
+    lo = contig(list_off, torch.int64)
+    plan = ivf_plan(pr, lo)
+    if total_rows is None:
+        total_rows = int(plan["slot_off"][-1].item())
+    out_s = torch.empty((Q, k), dtype=torch.float32, device=q.device)
+    out_i = torch.empty((Q, k), dtype=torch.int64, device=q.device)
+    out_n = torch.empty((Q,), dtype=torch.int32, device=q.device)
+    nbytes = int(_lib.fn("irc_ivf_topk_workspace")(Q, nprobe, int(total_rows), k))
+    ws = workspace(nbytes, q.device, ws_tag)
+    _lib.call("irc_ivf_topk", ptr(q), ptr(d), ptr(rid), ptr(lo), lo.numel() - 1, ptr(pr),
+              ptr(plan["slot_off"]), ptr(plan["cand_off"]), ptr(plan["pair_order"]),
+              ptr(plan["seg_off"]), ptr(plan["chunk_off"]), Q, nprobe, N, D, k, int(total_rows),
+              int(max_list_rows), ptr(ws), ws.numel(), ptr(out_s), ptr(out_i), ptr(out_n),
+              stream_ptr(q.device))
+    return out_s, out_i, out_n
 
 
 def shard_bounds(n_docs: int, world: int, rank: int):
@@ -1027,6 +1130,177 @@ class ShardedDenseIndex:
             slots.append((g, qin, so, io, ws))
         cache[key] = slots
         return slots
+
+
+class IVFDenseIndex(ShardedDenseIndex):
+    """A shard of the corpus as an inverted-file (IVF) index: the rows clustered into ``nlist``
+    lists, a search scoring only the ``nprobe`` lists nearest to each query.
+
+    Everything approximate lies in WHICH lists are probed; their rows are ranked exactly.
+    ``search(queries, k, nprobe)`` is, per query, the exact top-k over the union of the rows of
+    its probed lists, by (score desc, global id asc), padding (-inf, -1), n[q] = min(k, rows in
+    the probed lists).  With ``nprobe == nlist`` it is ``ShardedDenseIndex.search``'s ranking.
+    Ids are global ids of the ORIGINAL corpus (``doc_offset`` + original row), so per-shard
+    results merge with ``topk_merge`` as the scan's do.  bf16 only.
+
+    Attributes: ``docs`` [N, D] bf16, the rows in list order (the only copy); ``row_id`` int32
+    [N], each row's global id; ``list_off`` int64 [nlist + 1]; ``centroids`` [nlist, D] bf16;
+    ``max_list_rows`` (host int, the longest list).
+
+    Build it with ``train`` (k-means on the device) or ``from_lists`` (the caller's own
+    clustering); the plain constructor is not the way in."""
+
+    def __init__(self, *args, **kwargs):
+        raise TypeError("build an IVFDenseIndex with IVFDenseIndex.train(...) or "
+                        "IVFDenseIndex.from_lists(...)")
+
+    @classmethod
+    def from_lists(cls, docs: torch.Tensor, centroids: torch.Tensor, assign: torch.Tensor,
+                   doc_offset: int = 0, group=None, dtype: str = "bf16"):
+        """The index over a caller's clustering: ``assign`` [N] gives each row of ``docs`` its
+        list in [0, nlist), ``centroids`` [nlist, D] is what ``probe`` ranks the lists by (inner
+        product).  One host synchronisation (the longest list)."""
+        if dtype != "bf16":
+            raise ValueError(f"IVFDenseIndex is bf16 only (e4m3 lists are a follow-up), not "
+                             f"dtype={dtype!r}")
+        if docs.dim() != 2 or centroids.dim() != 2 or centroids.shape[1] != docs.shape[1]:
+            raise ValueError(f"docs {tuple(docs.shape)} and centroids {tuple(centroids.shape)} "
+                             "must be [N, D] and [nlist, D]")
+        if assign.numel() != docs.shape[0]:
+            raise ValueError(f"assign has {assign.numel()} entries for {docs.shape[0]} rows")
+        if doc_offset < 0 or doc_offset + docs.shape[0] >= 2 ** 31:
+            raise ValueError("global doc ids must fit int32 (doc_offset + N < 2^31)")
+        nlist = centroids.shape[0]
+        order, list_off = ivf_layout(assign.to(docs.device), nlist)
+        self = cls.__new__(cls)
+        self.dtype = "bf16"
+        self.fp8_scale = float(FP8_SCALE)
+        self.docs = docs.to(torch.bfloat16)[order].contiguous()
+        self.row_id = (order + int(doc_offset)).to(torch.int32)
+        self.list_off = list_off
+        self.centroids = centroids.to(device=docs.device, dtype=torch.bfloat16).contiguous()
+        self.max_list_rows = int((list_off[1:] - list_off[:-1]).max().item()) if nlist else 0
+        self.doc_offset = int(doc_offset)
+        self.group = group
+        return self
+
+    @classmethod
+    def train(cls, docs: torch.Tensor, nlist: int, doc_offset: int = 0, group=None,
+              niter: int = 20, nredo: int = 1, seed: int = 0, dtype: str = "bf16"):
+        """Cluster ``docs`` [N, D] into ``nlist`` lists and build the index: ``cluster.kmeans`` on
+        the fp32 rows, the centroids L2-normalised as the reference's run_kmeans leaves its
+        prototypes (src/contrastor/utils.py:98), then every row assigned to the centroid of
+        LARGEST INNER PRODUCT -- the probe ranks lists by inner product, so the assignment
+        does too (``cluster._assign`` over the normalised centroids with a zero bias).  The
+        centroids are kept as bf16.  Under a launcher each rank trains over its own shard."""
+        from . import cluster
+
+        if dtype != "bf16":
+            raise ValueError(f"IVFDenseIndex is bf16 only (e4m3 lists are a follow-up), not "
+                             f"dtype={dtype!r}")
+        require_hip(docs)
+        x = docs.float().contiguous()
+        c, _, _ = cluster.kmeans(x, nlist, niter=niter, nredo=nredo, seed=seed)
+        # the bf16 centroids are what the probe ranks by, so the rows are assigned by them too
+        c = torch.nn.functional.normalize(c, dim=1).to(torch.bfloat16)
+        bias = torch.zeros((nlist,), dtype=torch.float32, device=x.device)
+        assign, _ = cluster._assign(x, c.float().contiguous(), bias)
+        return cls.from_lists(docs, c, assign, doc_offset, group)
+
+    # ------------------------------------------------------------ persistence
+    def save(self, directory: str, rank: int = 0, doc_ids=None) -> None:
+        """The parent's files (the rows in list order) and ``ivf_{rank}.npz``: the centroids'
+        bf16 bits, ``list_off`` and ``row_id``."""
+        import os
+
+        import numpy as np
+
+        super().save(directory, rank, doc_ids)
+        np.savez(os.path.join(directory, f"ivf_{rank}.npz"),
+                 centroids=self.centroids.view(torch.uint16).cpu().numpy(),
+                 list_off=self.list_off.cpu().numpy(), row_id=self.row_id.cpu().numpy())
+
+    @classmethod
+    def load(cls, directory: str, rank: int = 0, device=None, group=None):
+        import os
+
+        import numpy as np
+
+        self, doc_dict = super().load(directory, rank, device, group)
+        if self.dtype != "bf16":
+            raise ValueError(f"IVFDenseIndex is bf16 only, the saved shard is {self.dtype}")
+        dev = self.docs.device
+        with np.load(os.path.join(directory, f"ivf_{rank}.npz")) as z:
+            self.centroids = torch.from_numpy(z["centroids"]).to(dev).view(torch.bfloat16)
+            self.list_off = torch.from_numpy(z["list_off"]).to(dev)
+            self.row_id = torch.from_numpy(z["row_id"]).to(dev)
+        lens = self.list_off[1:] - self.list_off[:-1]
+        self.max_list_rows = int(lens.max().item()) if lens.numel() else 0
+        return self, doc_dict
+
+    # ------------------------------------------------------------ search
+    def _check_nprobe(self, nprobe):
+        nlist = self.centroids.shape[0]
+        if not 1 <= nprobe <= min(nlist, 1024):
+            raise ValueError(f"nprobe={nprobe} outside [1, min(nlist={nlist}, 1024)]")
+
+    def probe(self, queries: torch.Tensor, nprobe: int) -> torch.Tensor:
+        """The ``nprobe`` lists nearest to each query, int32 [Q, nprobe]: ``scan_topk`` over the
+        centroids -- inner product desc, ties to the lower list id."""
+        self._check_nprobe(nprobe)
+        return scan_topk(queries, self.centroids, nprobe, ws_tag="ivf_probe")[1].to(torch.int32)
+
+    def _local_ivf(self, queries, k, nprobe, probe, ws_tag):
+        """This shard's probe and ``ivf_topk``: the whole of a single-process search, step (2)
+        of a sharded one."""
+        if probe is None:
+            probe = self.probe(queries, nprobe)
+        return ivf_topk(queries, self.docs, self.row_id, self.list_off, probe, k,
+                        self.max_list_rows, ws_tag=ws_tag)
+
+    def search(self, queries: torch.Tensor, k: int, nprobe=None, probe=None,
+               equal_counts: bool = False, ws_tag: str = "ivf", group_off=None):
+        """(scores [Q, k], idx [Q, k] global ids, n [Q]): each query's exact top-k over the rows
+        of its probed lists.  Exactly one of ``nprobe`` (this index's own ``probe``) and
+        ``probe`` (int32 [Q, nprobe], the caller's lists, -1 = none) is given.
+
+        Over a process group it is the scan's three steps with the middle one replaced: the
+        queries are all-gathered, every shard probes ``nprobe`` of ITS OWN lists and ranks
+        their rows, the per-shard lists are all-gathered and merged; n is the count of filled
+        slots.  ``probe=`` is then an error (lists are per shard).  Every argument check runs
+        before the first collective."""
+        if group_off is not None:
+            raise NotImplementedError("IVFDenseIndex.search(group_off=): the rows are permuted, "
+                                      "so groups are no row ranges; a follow-up")
+        if (nprobe is None) == (probe is None):
+            raise ValueError("give exactly one of nprobe and probe")
+        if not 1 <= k <= 1024:
+            raise ValueError(f"k={k} outside [1, 1024]")
+        if queries.dim() != 2 or queries.shape[1] != self.docs.shape[1]:
+            raise ValueError(f"dim mismatch: queries {tuple(queries.shape)}, docs "
+                             f"D={self.docs.shape[1]}")
+        if nprobe is not None:
+            self._check_nprobe(nprobe)
+        elif self._sharded():
+            raise ValueError("probe= over a process group: lists are per shard, pass nprobe")
+        elif probe.dim() != 2 or probe.shape[0] != queries.shape[0] or \
+                not 1 <= probe.shape[1] <= self.centroids.shape[0]:
+            raise ValueError(f"probe must be [Q, 1 .. nlist] for {queries.shape[0]} queries, "
+                             f"not {tuple(probe.shape)}")
+        if not self._sharded():
+            return self._local_ivf(queries, k, nprobe, probe, ws_tag)
+        allq = self._gather_queries(queries, equal_counts)  # (1)
+        s, i, _ = self._local_ivf(allq, k, nprobe, None, ws_tag)  # (2)
+        ms, mi = self._exchange_merge(s, i, k)  # (3)
+        return ms, mi, (mi >= 0).sum(dim=1).to(torch.int32)
+
+    def search_candidates(self, *args, **kwargs):
+        raise NotImplementedError("IVFDenseIndex.search_candidates: candidate ids name original "
+                                  "rows and the rows are permuted; a follow-up")
+
+    def search_many(self, *args, **kwargs):
+        raise NotImplementedError("IVFDenseIndex.search_many: the pipelined form is built on "
+                                  "the scan's native loop; a follow-up")
 
 
 _GRAPH_SERIAL = itertools.count()  # unique workspace tags of captured searches

@@ -4,7 +4,7 @@
                    [--model LSTM|BERT] [--loss InfoNCE] [--opt adam] [--sample uniform|tf_idf]
                    [--seed 1337] [--logdir log] [--ckptdir ckpt] [--retrieval sparse|dense|hybrid]
                    [--rerank-method auto|gather|stream] [--rerank-unit line|page]
-                   [--index-dtype bf16|fp8]
+                   [--index-dtype bf16|fp8] [--index flat|ivf] [--nlist N] [--nprobe P]
 
 Multi-GPU (one process per GPU):
     torchrun --nproc-per-node N --master-addr 127.0.0.1 main.py [same flags]
@@ -21,7 +21,9 @@ the reference's sparse candidate filter per claim (default) or, with
 ``--retrieval hybrid``, that top-k over each claim's filter candidates only (the
 reference's two stages joined).  With either of the two, ``--rerank-unit page`` ranks the
 k best pages, each by its best line, instead of the k best lines.  The compute runs on the
-MI355X HIP kernels only:
+``--index ivf`` (dense only) clusters the evidence corpus into ``--nlist`` lists and scores
+only the ``--nprobe`` lists nearest to each claim -- exactly, so what it trades for speed is
+which lists are looked at.  The compute runs on the MI355X HIP kernels only:
 ``--gpu -1`` (CPU) is rejected -- there is no CPU fallback in this build.
 """
 import argparse
@@ -82,7 +84,29 @@ def get_args(argv=None):
                         "bf16 (default), or fp8: e4m3 bytes at half the size, the claims "
                         "quantised with the same scale per search and the scores those of "
                         "the quantised embeddings")
-    return p.parse_args(argv)
+    p.add_argument("--index", default="flat", type=str, choices=["flat", "ivf"],
+                   help="--retrieval dense: flat (default) scans the whole evidence corpus; "
+                        "ivf clusters it into --nlist lists (k-means on the device; under a "
+                        "launcher each rank over its own slice) and ranks, exactly, only the "
+                        "rows of the --nprobe lists nearest to each claim")
+    p.add_argument("--nlist", default=1024, type=int,
+                   help="--index ivf: lists the corpus (each rank's slice) is clustered into")
+    p.add_argument("--nprobe", default=8, type=int,
+                   help="--index ivf: lists probed per claim (per shard), 1 .. min(nlist, 1024)")
+    args = p.parse_args(argv)
+    if args.index == "ivf":
+        if args.retrieval == "hybrid":
+            p.error("--index ivf ranks the probed lists, not a candidate filter's rows: it "
+                    "goes with --retrieval dense, not hybrid")
+        if args.rerank_unit == "page":
+            p.error("--index ivf has no per-page unit yet (the rows are permuted): use "
+                    "--rerank-unit line")
+        if args.index_dtype == "fp8":
+            p.error("--index ivf keeps bf16 lists only: use --index-dtype bf16")
+        if args.nlist < 1 or not 1 <= args.nprobe <= min(args.nlist, 1024):
+            p.error(f"--index ivf needs --nlist >= 1 and 1 <= --nprobe <= min(nlist, 1024), "
+                    f"not nlist={args.nlist} nprobe={args.nprobe}")
+    return args
 
 
 def resolve_device(gpu: str) -> torch.device:

@@ -113,8 +113,13 @@ def predict_dense(args, k=100):
     ``args.rerank_unit == "page"`` (main.py --rerank-unit): the k best PAGES, each by its
     best line, instead of the k best lines -- ``search(..., group_off=row_off)``, the page
     -> row range map built while the lines are enumerated -- and the recall printed is
-    over k pages, as the FEVER labels count."""
-    from irc_amd.retrieval import shard_bounds
+    over k pages, as the FEVER labels count.
+
+    ``args.index == "ivf"`` (main.py --index): the shard becomes an ``IVFDenseIndex`` of
+    ``args.nlist`` lists, each rank training over its own slice, and a search ranks the rows
+    of the ``args.nprobe`` lists nearest to each claim (per shard); the recall line names
+    both.  With every list probed it is the flat index's ranking."""
+    from irc_amd.retrieval import IVFDenseIndex, shard_bounds
 
     assert args.ckpt is not None
     _, model, _, _ = load_model(args.ckpt)
@@ -135,8 +140,15 @@ def predict_dense(args, k=100):
     by_page = getattr(args, "rerank_unit", "line") == "page"
     row_off = torch.tensor(row_off, dtype=torch.int64, device=args.device) if by_page else None
     lo, hi = shard_bounds(len(texts), world, rank)
-    index = ShardedDenseIndex(encode_corpus(model, texts[lo:hi], args.device), doc_offset=lo,
-                              group=group, dtype=getattr(args, "index_dtype", "bf16"))
+    ivf = getattr(args, "index", "flat") == "ivf"
+    if ivf:
+        if by_page or getattr(args, "index_dtype", "bf16") != "bf16":
+            raise ValueError("--index ivf: bf16 lists and the line unit only")
+        index = IVFDenseIndex.train(encode_corpus(model, texts[lo:hi], args.device), args.nlist,
+                                    doc_offset=lo, group=group, seed=getattr(args, "seed", 0))
+    else:
+        index = ShardedDenseIndex(encode_corpus(model, texts[lo:hi], args.device), doc_offset=lo,
+                                  group=group, dtype=getattr(args, "index_dtype", "bf16"))
     dim = model.loss_config["dim"]
     hits = total = 0
     for batch in tqdm(loader, desc="Iteration", disable=rank != 0):
@@ -147,7 +159,10 @@ def predict_dense(args, k=100):
         q = model.ctx2vec(mine, args.device) if mine else \
             torch.empty((0, dim), dtype=torch.float32, device=args.device)
         # rows: the whole batch, in order
-        idx = index.search(q, k, group_off=row_off)[1] if by_page else index.search(q, k)[1]
+        if ivf:
+            idx = index.search(q, k, nprobe=args.nprobe)[1]
+        else:
+            idx = index.search(q, k, group_off=row_off)[1] if by_page else index.search(q, k)[1]
         torch.cuda.synchronize()
         if rank == 0:
             print(f"batch of {len(claims)} claims: {time.time() - s:.4f}s")
@@ -157,7 +172,9 @@ def predict_dense(args, k=100):
             hits += int(any(titles[j] in gold for j in row if j >= 0))
             total += 1
     if rank == 0:
-        print(f"evidence recall@{k}{' (pages)' if by_page else ''}: {hits / max(total, 1):.4f}")
+        unit = f" (ivf nlist={args.nlist} nprobe={args.nprobe})" if ivf else \
+            (" (pages)" if by_page else "")
+        print(f"evidence recall@{k}{unit}: {hits / max(total, 1):.4f}")
     return hits / max(total, 1)
 
 
