@@ -314,6 +314,65 @@ int irc_ivf_topk(const void* queries, const void* docs, const int32_t* row_id,
                  void* workspace, int64_t workspace_bytes, float* out_score, int64_t* out_idx,
                  int32_t* out_n, irc_stream_t stream);
 
+/* The plan of one cluster-pruned search, built on the device: slot_off [Q * nprobe + 1],
+ * cand_off [Q + 1], pair_order [Q * nprobe], seg_off [nlist + 1] and chunk_off [nlist + 1] as
+ * irc_ivf_topk reads them, elementwise what retrieval.ivf_plan (the documented form) computes
+ * from probe [Q, nprobe] and list_off [nlist + 1] -- the invalid pairs in ascending order in
+ * pair_order's tail included.  probe holds int32 ids, or int64 ids (irc_scan_topk's out_idx)
+ * when probe_is_i64 != 0; an id outside [0, nlist) names no list, owns no keys and sorts behind
+ * every list.  Rows are unique by contract (a repeated id is marked once: the plan then differs
+ * from ivf_plan's, but every index stays inside its array).
+ *
+ * Integer arithmetic only, deterministic, stream-ordered, no workgroup waits on another: bit
+ * (c, q) of an nlist x ceil(Q / 32)-word bitmap is OR-ed in for every pair, a list's pair
+ * count is its row's popcount, the stable rank of pair (q, j) in list c the popcount of row c
+ * below bit q, and the offsets are reduce / scan / propagate passes in which one workgroup
+ * covers irc_ivf_plan_span() elements.  All scratch lies in the workspace
+ * (irc_ivf_plan_workspace; contents before the call do not matter).
+ *
+ * Validation, in this order, each IRC_E_INVALID with a message that starts "ivf_plan:" and
+ * found before any device work: no negative size; 1 <= nprobe <= nlist; Q * nprobe < 2^30 (and
+ * Q, nlist < 2^31 - 1); then the workspace (IRC_E_WORKSPACE, both sizes in the message).
+ * Q == 0 returns IRC_OK there and touches nothing; else no null array. */
+int irc_ivf_plan_span(void);
+int64_t irc_ivf_plan_workspace(int64_t Q, int64_t nprobe, int64_t nlist);
+int irc_ivf_plan(const void* probe, int probe_is_i64, const int64_t* list_off, int64_t Q,
+                 int64_t nprobe, int64_t nlist, void* workspace, int64_t workspace_bytes,
+                 int64_t* slot_off, int64_t* cand_off, int32_t* pair_order, int64_t* seg_off,
+                 int64_t* chunk_off, irc_stream_t stream);
+
+/* A whole cluster-pruned search in one call, stream-ordered (no host synchronisation, so it
+ * can be captured in a graph and issued back to back): on `stream`, in order, the probe --
+ * irc_scan_topk of the queries over centroids [nlist, D] bf16 with k = nprobe, when probe is
+ * null; else the caller's probe [Q, nprobe] int32 is used as irc_ivf_topk uses it -- then
+ * irc_ivf_plan's kernels, then irc_ivf_topk's scoring pass and select.  Same arrays, same
+ * ranking and the same bits as irc_ivf_topk over retrieval.ivf_plan's plan.
+ *
+ * The key count is only known on the device, so the host passes a bound: key_rows >= Q x (the
+ * sum of the nprobe longest lists) holds for every probe with unique rows.  It sizes the key
+ * region and is the scoring kernel's and the select's n_keys: a probe that breaks the contract
+ * may be ranked wrongly, but nothing is read or written past the workspace.  Workspace
+ * (irc_ivf_search_workspace; D does not enter, the probe's part is the largest over the
+ * supported widths): the keys, the five plan arrays, the plan's scratch, and the probe's
+ * outputs and scan workspace.  Contents before the call do not matter, and the slack of the
+ * bound is never read.  out_probe (may be null): int32 [Q, nprobe], the probe that was used.
+ *
+ * Validation, in this order, each IRC_E_INVALID with a message that starts "ivf_search:" and
+ * found before any device work: no negative size; 1 <= k <= 1024; D as irc_scan_topk accepts;
+ * 1 <= nprobe <= nlist (and <= 1024 when the call probes itself); N < 2^31; Q * nprobe < 2^30;
+ * max_list_rows <= N and <= 65535 segments; then the workspace (IRC_E_WORKSPACE, required and
+ * given sizes in the message).  Q == 0 returns IRC_OK there and touches nothing; else no null
+ * array (docs may be null when N == 0; one of probe and centroids is given) and queries, docs
+ * and centroids 16-byte aligned. */
+int64_t irc_ivf_search_workspace(int64_t Q, int64_t nprobe, int64_t nlist, int64_t key_rows,
+                                 int64_t k);
+int irc_ivf_search(const void* queries, const void* docs, const int32_t* row_id,
+                   const int64_t* list_off, int64_t nlist, const void* centroids,
+                   const int32_t* probe, int64_t Q, int64_t nprobe, int64_t N, int64_t D,
+                   int64_t k, int64_t key_rows, int64_t max_list_rows, void* workspace,
+                   int64_t workspace_bytes, float* out_score, int64_t* out_idx, int32_t* out_n,
+                   int32_t* out_probe, irc_stream_t stream);
+
 /* Raw score tile for tests / diagnostics: out[Q, N] fp32 = queries . docs^T
  * using the same MFMA path as irc_scan_topk. */
 int irc_scan_scores(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,

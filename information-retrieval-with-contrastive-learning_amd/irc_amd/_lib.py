@@ -61,6 +61,12 @@ SIGNATURES = {
     "irc_ivf_topk_workspace": (I64, [I64, I64, I64, I64]),
     "irc_ivf_topk": (I32, [P, P, P, P, I64, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64,
                            P, I64, P, P, P, P]),
+    "irc_ivf_plan_span": (I32, []),
+    "irc_ivf_plan_workspace": (I64, [I64, I64, I64]),
+    "irc_ivf_plan": (I32, [P, I32, P, I64, I64, I64, P, I64, P, P, P, P, P, P]),
+    "irc_ivf_search_workspace": (I64, [I64, I64, I64, I64, I64]),
+    "irc_ivf_search": (I32, [P, P, P, P, I64, P, P, I64, I64, I64, I64, I64, I64, I64, P, I64, P,
+                             P, P, P, P]),
     "irc_scan_topk_fp8_workspace": (I64, [I64, I64, I64, I64]),
     "irc_scan_topk_fp8": (I32, [P, P, I64, I64, I64, I64, I64, F32, P, I64, P, P, P]),
     "irc_scan_scores_fp8": (I32, [P, P, I64, I64, I64, P, P]),

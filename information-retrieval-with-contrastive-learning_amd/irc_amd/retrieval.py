@@ -17,8 +17,10 @@ that unit too: ``search(..., group_off=)`` returns the top-k groups of the whole
 (``scan_topk_grouped``), each shard over its own slice of the groups (``local_group_slice``).
 
 Cluster-pruned search: ``IVFDenseIndex`` keeps a shard clustered into lists and a search ranks,
-exactly, only the rows of the lists nearest to each query (``ivf_topk``); sharded as the scan is,
-each shard probing its own lists.
+exactly, only the rows of the lists nearest to each query; sharded as the scan is, each shard
+probing its own lists.  A search is one stream-ordered native call (``ivf_search``: probe, the
+plan built on the device, scoring, select); ``ivf_plan`` + ``ivf_topk`` are the same search with
+the plan built in torch, the documented form and the oracle of the native one.
 """
 from __future__ import annotations
 
@@ -655,6 +657,118 @@ def ivf_topk(queries: torch.Tensor, docs: torch.Tensor, row_id: torch.Tensor,
     return out_s, out_i, out_n
 
 
+def ivf_plan_native(probe: torch.Tensor, list_off: torch.Tensor, ws_tag: str = "ivf_plan"):
+    """``ivf_plan`` built by the library's kernels (irc_ivf_plan): the same dict, elementwise
+    equal for every probe with unique rows, in a handful of launches with no sort and no host
+    synchronisation.  ``probe`` [Q, nprobe] int32 or int64 (``scan_topk``'s ids as they are),
+    ``list_off`` [nlist + 1]; both on one HIP device.  ``ivf_plan`` stays the documented form
+    of the plan and the oracle of this one."""
+    if probe.dim() != 2:
+        raise ValueError(f"probe must be [Q, nprobe], not {tuple(probe.shape)}")
+    if probe.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"probe must be int32 or int64, not {probe.dtype}")
+    if list_off.dim() != 1 or list_off.numel() < 1:
+        raise ValueError(f"list_off must be [nlist + 1], not {tuple(list_off.shape)}")
+    require_hip(probe, list_off)
+    pr = probe.contiguous()
+    lo = contig(list_off, torch.int64)
+    Q, nprobe = pr.shape
+    nlist = lo.numel() - 1
+    dev = pr.device
+    new = torch.empty if Q else torch.zeros  # the call writes every element, or (Q == 0) none
+    plan = {"slot_off": new(Q * nprobe + 1, dtype=torch.int64, device=dev),
+            "cand_off": new(Q + 1, dtype=torch.int64, device=dev),
+            "pair_order": new(Q * nprobe, dtype=torch.int32, device=dev),
+            "seg_off": new(nlist + 1, dtype=torch.int64, device=dev),
+            "chunk_off": new(nlist + 1, dtype=torch.int64, device=dev)}
+    nbytes = int(_lib.fn("irc_ivf_plan_workspace")(Q, nprobe, nlist))
+    ws = workspace(nbytes, dev, ws_tag)
+    _lib.call("irc_ivf_plan", ptr(pr), int(pr.dtype == torch.int64), ptr(lo), Q, nprobe, nlist,
+              ptr(ws), ws.numel(), ptr(plan["slot_off"]), ptr(plan["cand_off"]),
+              ptr(plan["pair_order"]), ptr(plan["seg_off"]), ptr(plan["chunk_off"]),
+              stream_ptr(dev))
+    return plan
+
+
+def ivf_search(queries: torch.Tensor, docs: torch.Tensor, row_id: torch.Tensor,
+               list_off: torch.Tensor, k: int, key_rows: int, max_list_rows: int,
+               centroids=None, nprobe=None, probe=None, ws_tag: str = "ivf", out=None,
+               out_probe=None, ws=None):
+    """A whole cluster-pruned search in one native call (irc_ivf_search): the probe
+    (``scan_topk`` over ``centroids`` [nlist, D] with k = ``nprobe``) unless the caller's
+    ``probe`` int32 [Q, nprobe] is given, the plan on the device, ``ivf_topk``'s scoring pass
+    and select.  Stream-ordered: no host synchronisation and no torch op between them, so it
+    can be captured in a graph.  Same arrays and result as ``ivf_topk``, bit for bit.
+
+    ``key_rows`` is a host bound on the keys of the call, Q x (the sum of the nprobe longest
+    lists) or more (``IVFDenseIndex.key_bound``).  ``out`` = (scores [Q, k] fp32, idx [Q, k]
+    int64, n [Q] int32), contiguous, is written in place when given; ``out_probe`` int32
+    [Q, nprobe] receives the probe that was used; ``ws`` is the caller's own workspace (uint8,
+    at least irc_ivf_search_workspace bytes) instead of the cached one."""
+    if queries.dim() != 2 or docs.dim() != 2 or docs.shape[1] != queries.shape[1]:
+        raise ValueError(f"dim mismatch: queries {tuple(queries.shape)}, docs "
+                         f"{tuple(docs.shape)}")
+    if (nprobe is None) == (probe is None):
+        raise ValueError("give exactly one of nprobe and probe")
+    Q, D = queries.shape
+    N = docs.shape[0]
+    nlist = list_off.numel() - 1
+    if probe is not None:
+        if probe.dim() != 2 or probe.shape[0] != Q:
+            raise ValueError(f"probe must be [Q, nprobe] for {Q} queries, not "
+                             f"{tuple(probe.shape)}")
+        nprobe = probe.shape[1]
+    elif centroids is None or centroids.dim() != 2 or tuple(centroids.shape) != (nlist, D):
+        raise ValueError(f"centroids must be [nlist={nlist}, D={D}] to probe {nprobe} lists, "
+                         f"not {None if centroids is None else tuple(centroids.shape)}")
+    if row_id.numel() != N:
+        raise ValueError(f"row_id has {row_id.numel()} entries for {N} rows")
+    if out is not None and (tuple(out[0].shape) != (Q, k) or out[0].dtype != torch.float32 or
+                            tuple(out[1].shape) != (Q, k) or out[1].dtype != torch.int64 or
+                            tuple(out[2].shape) != (Q,) or out[2].dtype != torch.int32 or
+                            not all(o.is_contiguous() for o in out)):
+        raise ValueError(f"out must be contiguous fp32 [{Q}, {k}], int64 [{Q}, {k}], int32 [{Q}]")
+    if out_probe is not None and (tuple(out_probe.shape) != (Q, nprobe) or
+                                  out_probe.dtype != torch.int32 or
+                                  not out_probe.is_contiguous()):
+        raise ValueError(f"out_probe must be contiguous int32 [{Q}, {nprobe}]")
+    require_hip(queries, docs, row_id, list_off, centroids, probe)
+    q = contig(queries, torch.bfloat16)
+    d = contig(docs, torch.bfloat16)
+    rid = contig(row_id, torch.int32)
+    lo = contig(list_off, torch.int64)
+    pr = None if probe is None else contig(probe, torch.int32)
+    cen = None if probe is not None else contig(centroids, torch.bfloat16)
+    if out is None:
+        out = (torch.empty((Q, k), dtype=torch.float32, device=q.device),
+               torch.empty((Q, k), dtype=torch.int64, device=q.device),
+               torch.empty((Q,), dtype=torch.int32, device=q.device))
+    nbytes = int(_lib.fn("irc_ivf_search_workspace")(Q, nprobe, nlist, int(key_rows), k))
+    if ws is None:
+        ws = workspace(nbytes, q.device, ws_tag)
+    _lib.call("irc_ivf_search", ptr(q), ptr(d), ptr(rid), ptr(lo), nlist, ptr(cen), ptr(pr), Q,
+              nprobe, N, D, k, int(key_rows), int(max_list_rows), ptr(ws), ws.numel(),
+              ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out_probe), stream_ptr(q.device))
+    return out
+
+
+def ivf_query_chunk(Q: int, max_bytes: int, nbytes_of) -> int:
+    """The queries one ``ivf_search`` call of a batch of Q takes under a workspace limit: Q when
+    ``nbytes_of(Q)`` (the workspace of a call of that many queries, non-decreasing) fits
+    ``max_bytes``, else the largest multiple of 32 that fits -- and 32 when none does: a chunk
+    of the kernel's 32 query columns is the least a call is cut to."""
+    if Q <= 32 or nbytes_of(Q) <= max_bytes:
+        return Q
+    lo, hi = 1, (Q - 1) // 32
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if nbytes_of(32 * mid) <= max_bytes:
+            lo = mid
+        else:
+            hi = mid - 1
+    return 32 * lo
+
+
 def shard_bounds(n_docs: int, world: int, rank: int):
     """Contiguous shard [start, stop) of rank `rank` (first n % world ranks get +1)."""
     base, rem = divmod(n_docs, world)
@@ -1145,21 +1259,42 @@ class IVFDenseIndex(ShardedDenseIndex):
 
     Attributes: ``docs`` [N, D] bf16, the rows in list order (the only copy); ``row_id`` int32
     [N], each row's global id; ``list_off`` int64 [nlist + 1]; ``centroids`` [nlist, D] bf16;
-    ``max_list_rows`` (host int, the longest list).
+    ``max_list_rows`` (host int, the longest list); ``max_workspace_bytes`` (the workspace one
+    native call may take; a larger batch runs in query chunks, same bits).
 
     Build it with ``train`` (k-means on the device) or ``from_lists`` (the caller's own
     clustering); the plain constructor is not the way in."""
 
+    KEY_BOUND_LISTS = 1024  # the longest lists whose prefix sums are kept: the most a probe ranks
+    max_workspace_bytes = 1 << 30
+
     def __init__(self, *args, **kwargs):
         raise TypeError("build an IVFDenseIndex with IVFDenseIndex.train(...) or "
                         "IVFDenseIndex.from_lists(...)")
+
+    def _set_list_bounds(self):
+        """One host synchronisation: the prefix sums of the longest lists' lengths, descending,
+        kept on the host (``key_bound``); ``max_list_rows`` is the first."""
+        lens = self.list_off[1:] - self.list_off[:-1]
+        top = torch.sort(lens, descending=True)[0][:self.KEY_BOUND_LISTS]
+        self._key_prefix = [int(x) for x in torch.cumsum(top, 0).tolist()]
+        self.max_list_rows = self._key_prefix[0] if self._key_prefix else 0
+
+    def key_bound(self, nprobe: int) -> int:
+        """The most rows a query's ``nprobe`` probed lists can hold: the sum of the ``nprobe``
+        longest lists.  A host int, no synchronisation; Q x key_bound(nprobe) bounds the keys
+        of a search of Q queries whatever they probe (rows unique)."""
+        if not 1 <= nprobe <= len(self._key_prefix):
+            raise ValueError(f"key_bound(nprobe={nprobe}): outside [1, {len(self._key_prefix)}], "
+                             "the longest lists kept")
+        return self._key_prefix[nprobe - 1]
 
     @classmethod
     def from_lists(cls, docs: torch.Tensor, centroids: torch.Tensor, assign: torch.Tensor,
                    doc_offset: int = 0, group=None, dtype: str = "bf16"):
         """The index over a caller's clustering: ``assign`` [N] gives each row of ``docs`` its
         list in [0, nlist), ``centroids`` [nlist, D] is what ``probe`` ranks the lists by (inner
-        product).  One host synchronisation (the longest list)."""
+        product).  One host synchronisation (the longest lists' lengths, ``key_bound``)."""
         if dtype != "bf16":
             raise ValueError(f"IVFDenseIndex is bf16 only (e4m3 lists are a follow-up), not "
                              f"dtype={dtype!r}")
@@ -1179,7 +1314,7 @@ class IVFDenseIndex(ShardedDenseIndex):
         self.row_id = (order + int(doc_offset)).to(torch.int32)
         self.list_off = list_off
         self.centroids = centroids.to(device=docs.device, dtype=torch.bfloat16).contiguous()
-        self.max_list_rows = int((list_off[1:] - list_off[:-1]).max().item()) if nlist else 0
+        self._set_list_bounds()
         self.doc_offset = int(doc_offset)
         self.group = group
         return self
@@ -1234,8 +1369,7 @@ class IVFDenseIndex(ShardedDenseIndex):
             self.centroids = torch.from_numpy(z["centroids"]).to(dev).view(torch.bfloat16)
             self.list_off = torch.from_numpy(z["list_off"]).to(dev)
             self.row_id = torch.from_numpy(z["row_id"]).to(dev)
-        lens = self.list_off[1:] - self.list_off[:-1]
-        self.max_list_rows = int(lens.max().item()) if lens.numel() else 0
+        self._set_list_bounds()
         return self, doc_dict
 
     # ------------------------------------------------------------ search
@@ -1251,12 +1385,36 @@ class IVFDenseIndex(ShardedDenseIndex):
         return scan_topk(queries, self.centroids, nprobe, ws_tag="ivf_probe")[1].to(torch.int32)
 
     def _local_ivf(self, queries, k, nprobe, probe, ws_tag):
-        """This shard's probe and ``ivf_topk``: the whole of a single-process search, step (2)
-        of a sharded one."""
-        if probe is None:
-            probe = self.probe(queries, nprobe)
-        return ivf_topk(queries, self.docs, self.row_id, self.list_off, probe, k,
-                        self.max_list_rows, ws_tag=ws_tag)
+        """This shard's probe, plan, scoring and select as one native call (``ivf_search``),
+        stream-ordered: the whole of a single-process search, step (2) of a sharded one.  A
+        batch whose workspace would pass ``max_workspace_bytes`` runs in query chunks
+        (``ivf_query_chunk``) that write their rows of the outputs in place: a list may be
+        streamed more often, no bit changes (one accumulation order per pair)."""
+        require_hip(queries, self.docs, probe)
+        Q = queries.shape[0]
+        nlist = self.centroids.shape[0]
+        if probe is not None:
+            nprobe = probe.shape[1]
+        kept = len(self._key_prefix)
+        if nprobe <= kept:
+            bound = self.key_bound(nprobe)
+        else:  # a caller's wider probe: none of the other lists is longer than the last one kept
+            bound = self._key_prefix[-1] + (nprobe - kept) * (
+                self._key_prefix[-1] - self._key_prefix[-2])
+        need = _lib.fn("irc_ivf_search_workspace")
+        step = ivf_query_chunk(Q, self.max_workspace_bytes,
+                               lambda c: int(need(c, nprobe, nlist, c * bound, k)))
+        out = (torch.empty((Q, k), dtype=torch.float32, device=queries.device),
+               torch.empty((Q, k), dtype=torch.int64, device=queries.device),
+               torch.empty((Q,), dtype=torch.int32, device=queries.device))
+        for lo in range(0, max(Q, 1), max(step, 1)):
+            hi = min(Q, lo + step)
+            ivf_search(queries[lo:hi], self.docs, self.row_id, self.list_off, k,
+                       (hi - lo) * bound, self.max_list_rows, centroids=self.centroids,
+                       nprobe=nprobe if probe is None else None,
+                       probe=None if probe is None else probe[lo:hi], ws_tag=ws_tag,
+                       out=tuple(o[lo:hi] for o in out))
+        return out
 
     def search(self, queries: torch.Tensor, k: int, nprobe=None, probe=None,
                equal_counts: bool = False, ws_tag: str = "ivf", group_off=None):

@@ -1,7 +1,7 @@
 """Cluster-pruned dense search (IVFDenseIndex) against the exact scan: what a probe buys.
 
-    python tools/ivf_probe.py [--n 250000] [--d 768] [--k 100] [--out profiles/ivf_probe.json]
-    python tools/ivf_probe.py --tables profiles/ivf_probe.json   # DESIGN.md's table
+    python tools/ivf_probe.py [--n 250000] [--d 768] [--k 100] [--out profiles/ivf_probe_native.json]
+    python tools/ivf_probe.py --tables profiles/ivf_probe_native.json   # DESIGN.md's table
 
 One MI355X, a clustered synthetic shard (N x D bf16 unit rows around N / 64 random centres,
 larger than the Infinity Cache at the default size), an IVFDenseIndex trained on it per nlist.
@@ -10,16 +10,23 @@ windows of back-to-back calls, the variants alternating window by window in one 
 medians and min-max over the rounds, the calls of a window cycling through `sets` independent
 query draws so that no call finds its rows of the call before in the Infinity Cache:
 
-  * ivf      IVFDenseIndex.search(q, k, nprobe): probe, plan, scoring, select, the one host
-             synchronisation of the plan included;
+  * ivf      IVFDenseIndex.search(q, k, nprobe): probe, plan, scoring and select issued by
+             one native call (irc_ivf_search), the plan built on the device, no host
+             synchronisation;
+  * torchplan  the same search with the plan built in torch: index.probe, then ivf_topk
+             (retrieval.ivf_plan's launches, its sort and the one host synchronisation) --
+             the call as it was before the native one, and what the native one is accepted
+             against: its median no higher than this one's median plus this one's own spread
+             (the range of its window medians over the rounds), results identical;
   * scan     the exact search of the same shard (retrieval.scan_topk), the yardstick;
   * compose  what the parent commit could build from its own parts: the same probe, then
              expand_ranges over the lists and rerank_topk(method="gather") -- context for
              where the new scoring kernel matters;
   * probe    the probe alone (scan_topk over the centroids), a call time.
 
-Then, in a profiled pass of the ivf call, the scoring and select kernels' own times (the
-library's per-launch events), and from the plan the bytes the scoring pass streams -- the sum
+Then, in a profiled pass of the ivf call, the plan kernels' time (the clear and the kernels of
+irc_ivf_plan as one record) and the scoring and select kernels' own times (the library's
+per-launch events), and from the plan the bytes the scoring pass streams -- the sum
 over lists of chunks x rows x D x 2 -- over the scoring time.  recall@k of the ivf result
 against the exact scan's is reported per cell, never asserted.  Prints a table to stderr and
 writes ONE JSON object to --out."""
@@ -58,17 +65,40 @@ def tables(path):
     for shape in r["shapes"]:
         print(f"\n{shape['N']:,} x {shape['D']} bf16, k = {r['k']}; call times in us "
               "(median of the windows)\n")
-        print("| nlist | nprobe | Q | ivf call | probe call | score kernel | select kernel | "
-              "scan call | parent's parts | streamed MB | score TB/s | shard touched | "
-              "recall@k | ivf / scan |")
-        print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+        if "torchplan_call_us" not in shape["cells"][0]:
+            _tables_before_the_native_call(shape)
+            continue
+        print("| nlist | nprobe | Q | ivf call | torch-plan call (spread) | accepted | "
+              "probe call | plan kernels | score kernel | select kernel | scan call | "
+              "parent's parts | streamed MB | score TB/s | shard touched | recall@k | "
+              "ivf / scan |")
+        print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
         for c in shape["cells"]:
+            lo, hi = c["torchplan_call_us_minmax"]
             print(f"| {c['nlist']} | {c['nprobe']} | {c['Q']} | {c['ivf_call_us']:.0f} | "
-                  f"{c['probe_call_us']:.0f} | {c['score_kernel_us']:.0f} | "
+                  f"{c['torchplan_call_us']:.0f} ({hi - lo:.0f}) | "
+                  f"{'yes' if c['accepted'] else 'NO'}{'' if c['identical'] else ', DIFFERS'} | "
+                  f"{c['probe_call_us']:.0f} | {c['plan_kernels_us']:.0f} | "
+                  f"{c['score_kernel_us']:.0f} | "
                   f"{c['select_kernel_us']:.0f} | {c['scan_call_us']:.0f} | "
                   f"{c['compose_call_us']:.0f} | {c['streamed_bytes'] / 1e6:.1f} | "
                   f"{c['score_TBps']:.2f} | {100 * c['touched_frac']:.1f} % | "
                   f"{c['recall']:.3f} | {c['ivf_call_us'] / c['scan_call_us']:.2f} |")
+
+
+def _tables_before_the_native_call(shape):
+    """The columns of a result file written before the torchplan variant existed."""
+    print("| nlist | nprobe | Q | ivf call | probe call | score kernel | select kernel | "
+          "scan call | parent's parts | streamed MB | score TB/s | shard touched | "
+          "recall@k | ivf / scan |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for c in shape["cells"]:
+        print(f"| {c['nlist']} | {c['nprobe']} | {c['Q']} | {c['ivf_call_us']:.0f} | "
+              f"{c['probe_call_us']:.0f} | {c['score_kernel_us']:.0f} | "
+              f"{c['select_kernel_us']:.0f} | {c['scan_call_us']:.0f} | "
+              f"{c['compose_call_us']:.0f} | {c['streamed_bytes'] / 1e6:.1f} | "
+              f"{c['score_TBps']:.2f} | {100 * c['touched_frac']:.1f} % | "
+              f"{c['recall']:.3f} | {c['ivf_call_us'] / c['scan_call_us']:.2f} |")
 
 
 def _clustered(n, d, centres, own, g, dev, chunk=65536):
@@ -112,7 +142,13 @@ def probe_shape(args, n, lib, dev):
                     rows, rows_off = retrieval.expand_ranges(pr, off, index.list_off)
                     return retrieval.rerank_topk(q, index.docs, rows, rows_off, args.k)
 
+                def torchplan(q):
+                    return retrieval.ivf_topk(q, index.docs, index.row_id, index.list_off,
+                                              index.probe(q, nprobe), args.k,
+                                              index.max_list_rows, ws_tag="ivf_torchplan")
+
                 timed = [("ivf", cycling(lambda q: index.search(q, args.k, nprobe=nprobe))),
+                         ("torchplan", cycling(torchplan)),
                          ("scan", cycling(lambda q: retrieval.scan_topk(q, docs, args.k))),
                          ("compose", cycling(compose)),
                          ("probe", cycling(lambda q: index.probe(q, nprobe)))]
@@ -138,9 +174,14 @@ def probe_shape(args, n, lib, dev):
                 torch.cuda.synchronize()
                 lib.irc_prof_enable(0)
                 score_us, select_us = _prof(lib, b"ivf_score"), _prof(lib, b"rerank_select")
+                plan_us = _prof(lib, b"ivf_plan")
                 # from the plans of the draws: bytes streamed, shard touched, recall
                 streamed = touched = hit = 0.0
+                identical = True
                 for q in qs:
+                    identical = identical and all(
+                        torch.equal(a, b) for a, b in
+                        zip(index.search(q, args.k, nprobe=nprobe), torchplan(q)))
                     pr = index.probe(q, nprobe)
                     plan = retrieval.ivf_plan(pr, index.list_off)
                     chunks = plan["chunk_off"][1:] - plan["chunk_off"][:-1]
@@ -155,14 +196,20 @@ def probe_shape(args, n, lib, dev):
                         "streamed_bytes": streamed / args.sets,
                         "touched_frac": touched / args.sets, "recall": hit / args.sets,
                         "score_kernel_us": score_us, "select_kernel_us": select_us,
+                        "plan_kernels_us": plan_us, "identical": identical,
                         "score_TBps": streamed / args.sets / (score_us * 1e-6) / 1e12
                         if score_us else 0.0, "reps": reps}
                 for m in t:
                     cell[f"{m}_call_us"] = statistics.median(t[m]) * 1e3
                     cell[f"{m}_call_us_minmax"] = [min(t[m]) * 1e3, max(t[m]) * 1e3]
+                spread = max(t["torchplan"]) - min(t["torchplan"])
+                cell["accepted"] = bool(identical and statistics.median(t["ivf"]) <=
+                                        statistics.median(t["torchplan"]) + spread)
                 cells.append(cell)
                 print(f"N={n} nlist={nlist:5d} nprobe={nprobe:3d} Q={Q:5d}  ivf "
-                      f"{cell['ivf_call_us']:8.1f} us (probe {cell['probe_call_us']:6.1f}, score "
+                      f"{cell['ivf_call_us']:8.1f} us (torch plan {cell['torchplan_call_us']:8.1f}"
+                      f"{'' if cell['accepted'] else ' NOT ACCEPTED'}; probe "
+                      f"{cell['probe_call_us']:6.1f}, plan {plan_us:6.1f}, score "
                       f"{score_us:8.1f}, select {select_us:7.1f})  scan "
                       f"{cell['scan_call_us']:8.1f} us  parts {cell['compose_call_us']:9.1f} us  "
                       f"{cell['streamed_bytes'] / 1e6:8.1f} MB {cell['score_TBps']:5.2f} TB/s  "
@@ -183,7 +230,7 @@ def main():
     ap.add_argument("--window-ms", type=float, default=40.0, help="timed work per window")
     ap.add_argument("--sets", type=int, default=4, help="independent query draws per cell")
     ap.add_argument("--niter", type=int, default=10, help="k-means iterations of the build")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ivf_probe.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ivf_probe_native.json"))
     ap.add_argument("--tables", metavar="FILE", help="print the tables of a result file")
     args = ap.parse_args()
     if args.tables:
@@ -195,7 +242,7 @@ def main():
     lib = _lib.load()
     dev = torch.device("cuda:0")
     shapes = [probe_shape(args, n, lib, dev) for n in args.n]
-    result = {"probe": "ivf_search_scan_compose", "device": torch.cuda.get_device_name(0),
+    result = {"probe": "ivf_native_torchplan_scan_compose", "device": torch.cuda.get_device_name(0),
               "k": args.k, "rounds": args.rounds, "window_ms": args.window_ms, "sets": args.sets,
               "kmeans_niter": args.niter, "shapes": shapes}
     with open(args.out, "w") as f:
