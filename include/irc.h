@@ -193,6 +193,36 @@ int irc_rerank_topk_grouped(const void* queries, const void* docs, int64_t Q, in
                             float* out_score, int64_t* out_idx, int32_t* out_n,
                             irc_stream_t stream);
 
+/* The candidate top-k by a FUSED score: candidate i is ranked by s_i + bias[i], where s_i is
+ * exactly the fp32 score the unbiased entry of the same flags computes for that (query, row)
+ * (for e4m3 the value after score_scale) and the sum is ONE fp32 addition -- not an FMA, and
+ * no weight is applied here: the caller scales its prior.  out_score holds the sums.
+ *
+ * bias [n_cand] fp32, parallel to cand: bias[i] belongs to FLAT candidate i, whether or not
+ * that candidate is eligible (an id of another shard still owns its slot, which is not read).
+ * flags as irc_rerank_topk_grouped.  group_off == NULL: ranked per row, as irc_rerank_topk /
+ * _stream / _fp8 / _stream_fp8 rank (n_groups is not read; under IRC_RERANK_STREAM the lists
+ * are ascending); else per group as irc_rerank_topk_grouped, the bias added BEFORE the
+ * collapse, so a group is represented by the row with the best fused score.  Everything else
+ * is irc_rerank_topk's rule: (score desc, id asc), padding (-inf, -1), out_n[q] = min(k,
+ * eligible), ids outside the shard skipped.
+ *
+ * The values of bias are the caller's and are not checked: a non-finite sum is ranked as
+ * every score is keyed -- +inf first, then the finite values, then -inf, and NaN last of the
+ * eligible candidates (reported as a NaN); -0.0 counts as +0.0.
+ *
+ * Validation: irc_rerank_topk_grouped's sequence under the name rerank_topk_biased (the
+ * group checks only with group_off != NULL), and n_cand == 0 || bias != NULL ("null bias")
+ * after the candidate / docs pointer check.  The workspace is irc_rerank_topk_workspace
+ * without group_off, irc_rerank_topk_grouped_workspace with it; the bias is read in place. */
+int irc_rerank_biased_topk(const void* queries, const void* docs, int64_t Q, int64_t N,
+                           int64_t D, const int32_t* cand, const int64_t* cand_off,
+                           int64_t n_cand, int64_t k, int64_t doc_offset,
+                           const int64_t* group_off, int64_t n_groups, uint32_t flags,
+                           float score_scale, const float* bias, void* workspace,
+                           int64_t workspace_bytes, float* out_score, int64_t* out_idx,
+                           int32_t* out_n, irc_stream_t stream);
+
 /* Merge P per-shard GROUPED top-k lists: the reduce step of irc_rerank_topk_grouped over
  * several shards, as irc_topk_merge is of the scan.  A group whose best rows lie in two
  * shards is in two lists; irc_topk_merge would return it twice.

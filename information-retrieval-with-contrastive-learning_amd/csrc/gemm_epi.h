@@ -15,9 +15,12 @@ namespace gemm {
 // EPI_SCAN: the scan filter of gemm_pp.hip (see PArgs in gemm_pp.h); not an irc_gemm code
 // EPI_PICK: the candidate pick of gemm_pp.hip (irc_rerank_topk_stream); not an irc_gemm code
 // EPI_GROUP: the group maximum of gemm_pp.hip (irc_scan_topk_grouped); not an irc_gemm code
+// EPI_PICK_BIAS: EPI_PICK with a per-candidate bias added to the score
+// (irc_rerank_biased_topk); not an irc_gemm code
 enum Epi {
   EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_BIAS_RESID = 3, EPI_RESID = 4,
-  EPI_DGELU = 5, EPI_BIAS_GELU_SAVE = 6, EPI_SCAN = 7, EPI_PICK = 8, EPI_GROUP = 9
+  EPI_DGELU = 5, EPI_BIAS_GELU_SAVE = 6, EPI_SCAN = 7, EPI_PICK = 8, EPI_GROUP = 9,
+  EPI_PICK_BIAS = 10
 };
 // Not constexpr on purpose: a predicate the front end can fold reshapes the bias preload's
 // control flow in gemm_pp.hip, whose kernels sit at the 256-VGPR limit: all 57 of its

@@ -93,6 +93,10 @@ struct PArgs {
   // e4m3 pick (run_pick with fp8): the key's score is C[q][doc] * score_scale, a power of
   // two (exact); the bf16 pick does not read it
   float score_scale;
+  // biased pick (EPI_PICK_BIAS, run_pick with biased): `bias` above holds n_cand entries, one
+  // per flat candidate, and candidate j's key is make_key(score + bias[j], id), the addition
+  // one fp32 add after the e4m3 scale.  The field is the linear layers' column bias
+  // elsewhere; no pick reads it without `biased`.
   // group maximum (EPI_GROUP, run_group): every doc of the shard is a candidate of every
   // query.  Group g owns the global doc ids [group_off[g], group_off[g + 1]) (non-decreasing,
   // n_groups + 1 entries); gmax[q * n_groups + g], zeroed by the caller, receives the
@@ -121,7 +125,8 @@ void run_scan(const PArgs& a, hipStream_t st, bool fp8 = false);
 // M, N > 0 and ceil(M / 256) * ceil(N / 256) < 2^31
 // fp8: e4m3 operands, K / lda / ldb in 2-byte units (D/2, D % 128 == 0), keys scaled by
 // a.score_scale
-void run_pick(const PArgs& a, hipStream_t st, bool fp8 = false);
+// biased: EPI_PICK_BIAS, keys[j] ranks C[q][doc] (* score_scale) + a.bias[j], one fp32 addition
+void run_pick(const PArgs& a, hipStream_t st, bool fp8 = false, bool biased = false);
 // doc-tile width of run_pick
 constexpr int PICK_TILE = 256;
 // group maximum: A = queries [M=Q][K=D], B = docs [N][D], EPI_GROUP (see PArgs), the launch

@@ -863,7 +863,9 @@ __device__ __forceinline__ bool pick_ranges(const PArgs& g, char* lds, int m0, i
 // is read from the staged row at its column and its key goes to keys[j].  Nothing
 // depends on scheduling (no atomics: j is the candidate's own place).  A column outside
 // the tile (a list that broke the ascending contract) is skipped before any access.
-template <int F8 = 0>
+// BIAS (EPI_PICK_BIAS): the key's score is that score plus g.bias[j], one fp32 addition
+// after the e4m3 scale; the bias is loaded with the id, 4 of each in flight per lane.
+template <int F8 = 0, bool BIAS = false>
 __device__ __forceinline__ void epilogue_pick(const PArgs& g, const f32x4 (&acc)[8][4], char* lds,
                                               int m0, int n0, int grp, int wn, int lane) {
   float* S = reinterpret_cast<float*>(lds);
@@ -892,17 +894,23 @@ __device__ __forceinline__ void epilogue_pick(const PArgs& g, const f32x4 (&acc)
     const float* row = S + rq * 256;
     for (int64_t j0 = lo + seg; j0 < hi; j0 += 32) {
       int32_t id[4];
+      float bv[BIAS ? 4 : 1];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int64_t j = j0 + 8 * u;
         id[u] = j < hi ? g.cand[j] : 0;
+        if constexpr (BIAS) bv[u] = j < hi ? g.bias[j] : 0.f;
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int64_t j = j0 + 8 * u;
         const int64_t col = (int64_t)id[u] - first;
         if (j < hi && col >= 0 && col < nval) {
-          if constexpr (F8 != 0)
+          if constexpr (BIAS) {
+            float sc = row[(int)col ^ flip];
+            if constexpr (F8 != 0) sc *= g.score_scale;
+            g.keys[j] = make_key(add_bias(sc, bv[u]), (uint32_t)id[u]);
+          } else if constexpr (F8 != 0)
             g.keys[j] = make_key(row[(int)col ^ flip] * g.score_scale, (uint32_t)id[u]);
           else
             g.keys[j] = make_key(row[(int)col ^ flip], (uint32_t)id[u]);
@@ -1069,11 +1077,11 @@ __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
     split = rest % gridDim.z;
     batch = rest / gridDim.z;
   }
-  // EPI_SCAN (and EPI_PICK, EPI_GROUP): query tiles fastest, so the blocks of one doc tile
-  // run back to back on one XCD and read it from that XCD's L2 (C4: 2048 queries = 8 query
-  // tiles)
+  // EPI_SCAN (and EPI_PICK, EPI_PICK_BIAS, EPI_GROUP): query tiles fastest, so the blocks of
+  // one doc tile run back to back on one XCD and read it from that XCD's L2 (C4: 2048 queries
+  // = 8 query tiles)
   int tm, tn;
-  if (EPI == EPI_SCAN || EPI == EPI_PICK || EPI == EPI_GROUP) {
+  if (EPI == EPI_SCAN || EPI == EPI_PICK || EPI == EPI_PICK_BIAS || EPI == EPI_GROUP) {
     tm = bid % tiles_m;
     tn = bid / tiles_m;
   } else {
@@ -1091,7 +1099,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
   const int wn = wq;                          // 64-column slab of the tile
 
   if (EPI == EPI_SCAN) PSTAMP(0);
-  if constexpr (EPI == EPI_PICK) {
+  if constexpr (EPI == EPI_PICK || EPI == EPI_PICK_BIAS) {
     static_assert(AK && BK_ && F8 != 2, "the pick ranges live past two K-major buffers");
     if (!pick_ranges(g, lds, m0, n0)) return;  // no candidate in this tile
   }
@@ -1116,6 +1124,10 @@ __global__ __launch_bounds__(NT, 1) void gemm_pp_kernel(PArgs g) {
   }
   if constexpr (EPI == EPI_PICK) {
     epilogue_pick<F8>(g, acc, lds, m0, n0, grp, wn, lane);
+    return;
+  }
+  if constexpr (EPI == EPI_PICK_BIAS) {
+    epilogue_pick<F8, true>(g, acc, lds, m0, n0, grp, wn, lane);
     return;
   }
   if constexpr (EPI == EPI_GROUP) {
@@ -1386,9 +1398,15 @@ void run_scan(const PArgs& a, hipStream_t st, bool fp8) {
                        dim3(NT), 0, st, a);
 }
 
-void run_pick(const PArgs& a, hipStream_t st, bool fp8) {
+void run_pick(const PArgs& a, hipStream_t st, bool fp8, bool biased) {
   const int64_t tiles = ((int64_t)(a.M + 255) / 256) * ((a.N + 255) / 256);
-  if (fp8)
+  if (biased && fp8)
+    hipLaunchKernelGGL((gemm_pp_kernel<true, true, float, EPI_PICK_BIAS, 1>),
+                       dim3((unsigned)tiles), dim3(NT), 0, st, a);
+  else if (biased)
+    hipLaunchKernelGGL((gemm_pp_kernel<true, true, float, EPI_PICK_BIAS>),
+                       dim3((unsigned)tiles), dim3(NT), 0, st, a);
+  else if (fp8)
     hipLaunchKernelGGL((gemm_pp_kernel<true, true, float, EPI_PICK, 1>), dim3((unsigned)tiles),
                        dim3(NT), 0, st, a);
   else

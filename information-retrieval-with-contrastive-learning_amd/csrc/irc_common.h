@@ -245,6 +245,13 @@ __device__ __forceinline__ uint64_t make_key(float score, uint32_t gidx) {
   return ((uint64_t)orderable_f32(score) << 32) | (uint64_t)(uint32_t)(~gidx);
 }
 
+// score + bias as ONE fp32 addition: never contracted with the multiplication that made the
+// score (the e4m3 score_scale) into an FMA.  What the biased candidate top-k ranks by.
+__device__ __forceinline__ float add_bias(float score, float bias) {
+#pragma clang fp contract(off)
+  return score + bias;
+}
+
 // The group of global row id: the g with group_off[g] <= id < group_off[g + 1] (upper
 // bound, so repeated offsets -- empty groups -- are stepped over), -1 for a row of no group.
 // The search starts from RC_NS samples of group_off the workgroup keeps in LDS -- s_first =

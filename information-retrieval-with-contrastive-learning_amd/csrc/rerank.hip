@@ -39,6 +39,10 @@
 //  * irc_rerank_topk_grouped ranks groups of rows (pages) instead of rows: after any of the
 //    four scoring passes rerank_collapse_kernel zeroes every key that is not the maximum of
 //    its (query, group) run, and the unchanged select returns the top-k distinct groups.
+//  * irc_rerank_biased_topk ranks by score + bias[i] (hybrid retrieval's fused score: the
+//    sparse stage's per-candidate prior): the same four scoring passes with the addition as a
+//    compile-time variant -- score_chunk<E4M3, D, BIAS>, and EPI_PICK_BIAS in gemm_pp.hip --
+//    one fp32 add after the e4m3 scale, before the collapse when grouped.
 //  * irc_topk_merge_grouped is the reduce step of that call over several shards: the
 //    per-shard lists of a query hold one page twice when its best lines lie in two shards,
 //    so merge_collapse_kernel sorts the query's P * kin entries by row id (a group is a run
@@ -52,7 +56,7 @@
 // Layout: each thing exists once.  Device: score_chunk<E4M3, D> is the scoring body of both
 // gathered kernels (Operand<E4M3, D> holds what differs: piece type, pieces per lane, row
 // bytes, the dot product of a piece); chunk_owners is the owner search of the scoring and
-// the collapse kernels.  Host: the five extern "C" entries are one call of rerank_run each,
+// the collapse kernels.  Host: the six extern "C" entries are one call of rerank_run each,
 // which holds the argument checks (their order is part of the interface), then runs
 // score_gather (the D switch) or score_stream (the pick GEMM's arguments), the collapse if
 // grouped, and the select.  A new operand type is one more Operand; a new entry one more Form.
@@ -160,12 +164,15 @@ struct Operand<true, D> {  // e4m3 codes
 };
 
 // The scoring body of both gathered kernels: keys[i] of flat candidate i, one workgroup per
-// chunk of RR_CHUNK.  score_scale (a power of two: exact) applies to e4m3 only.
-template <bool E4M3, int D>
+// chunk of RR_CHUNK.  score_scale (a power of two: exact) applies to e4m3 only.  BIAS
+// (irc_rerank_biased_topk): the ranked score is the score plus bias[i], one fp32 addition
+// after the scale; without it bias is not read.
+template <bool E4M3, int D, bool BIAS = false>
 __device__ __forceinline__ void score_chunk(
     const char* __restrict__ queries, const char* __restrict__ docs, int Q, int64_t N,
     const int32_t* __restrict__ cand, const int64_t* __restrict__ cand_off, int64_t n_cand,
-    int64_t doc_offset, float score_scale, uint64_t* __restrict__ keys) {
+    int64_t doc_offset, float score_scale, uint64_t* __restrict__ keys,
+    const float* __restrict__ bias = nullptr) {
   typedef Operand<E4M3, D> Op;
   typedef typename Op::piece_t piece_t;
   constexpr int NC = Op::NC;  // pieces per lane per row
@@ -226,6 +233,9 @@ __device__ __forceinline__ void score_chunk(
     if (sub == r) myscore = acc;
   }
   if constexpr (E4M3) myscore *= score_scale;
+  if constexpr (BIAS) {
+    if (myrow >= 0) myscore = add_bias(myscore, bias[i]);
+  }
   if (i < n_cand) keys[i] = myrow >= 0 ? make_key(myscore, gid) : 0ull;
 }
 
@@ -248,6 +258,30 @@ __global__ __launch_bounds__(RR_CHUNK) void rerank_score_fp8_kernel(
   score_chunk<true, D>(reinterpret_cast<const char*>(queries),
                        reinterpret_cast<const char*>(docs), Q, N, cand, cand_off, n_cand,
                        doc_offset, score_scale, keys);
+}
+
+// The two gathered kernels with the per-candidate bias (irc_rerank_biased_topk): bias[i]
+// belongs to flat candidate i, as keys[i] does.
+template <int D>
+__global__ __launch_bounds__(RR_CHUNK) void rerank_score_bias_kernel(
+    const unsigned short* __restrict__ queries, const unsigned short* __restrict__ docs, int Q,
+    int64_t N, const int32_t* __restrict__ cand, const int64_t* __restrict__ cand_off,
+    int64_t n_cand, int64_t doc_offset, const float* __restrict__ bias,
+    uint64_t* __restrict__ keys) {
+  score_chunk<false, D, true>(reinterpret_cast<const char*>(queries),
+                              reinterpret_cast<const char*>(docs), Q, N, cand, cand_off, n_cand,
+                              doc_offset, 1.f, keys, bias);
+}
+
+template <int D>
+__global__ __launch_bounds__(RR_CHUNK) void rerank_score_fp8_bias_kernel(
+    const unsigned char* __restrict__ queries, const unsigned char* __restrict__ docs, int Q,
+    int64_t N, const int32_t* __restrict__ cand, const int64_t* __restrict__ cand_off,
+    int64_t n_cand, int64_t doc_offset, float score_scale, const float* __restrict__ bias,
+    uint64_t* __restrict__ keys) {
+  score_chunk<true, D, true>(reinterpret_cast<const char*>(queries),
+                             reinterpret_cast<const char*>(docs), Q, N, cand, cand_off, n_cand,
+                             doc_offset, score_scale, keys, bias);
 }
 
 __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
@@ -853,6 +887,8 @@ struct Form {
   bool grouped;              // top-k per group: the collapse between scoring and select
   const int64_t* group_off;  // grouped only (null is the caller's error)
   int64_t n_groups;
+  bool biased = false;         // irc_rerank_biased_topk: the ranked score is score + bias[i]
+  const float* bias = nullptr;  // biased only, [n_cand] (null is the caller's error)
 };
 
 }  // namespace rerank
@@ -890,7 +926,14 @@ static int score_gather(const Form& f, const void* queries, const void* docs, in
   prof_begin(st);
 #define IRC_RR_CASE(DD)                                                                         \
   case DD:                                                                                      \
-    if (f.e4m3)                                                                                 \
+    if (f.biased && f.e4m3)                                                                     \
+      hipLaunchKernelGGL((rerank_score_fp8_bias_kernel<DD>), dim3(blocks), dim3(RR_CHUNK), 0,   \
+                         st, qp8, dp8, (int)Q, N, cand, cand_off, n_cand, doc_offset,           \
+                         score_scale, f.bias, keys);                                            \
+    else if (f.biased)                                                                          \
+      hipLaunchKernelGGL((rerank_score_bias_kernel<DD>), dim3(blocks), dim3(RR_CHUNK), 0, st,   \
+                         qp, dp, (int)Q, N, cand, cand_off, n_cand, doc_offset, f.bias, keys);  \
+    else if (f.e4m3)                                                                            \
       hipLaunchKernelGGL((rerank_score_fp8_kernel<DD>), dim3(blocks), dim3(RR_CHUNK), 0, st,    \
                          qp8, dp8, (int)Q, N, cand, cand_off, n_cand, doc_offset, score_scale,  \
                          keys);                                                                 \
@@ -939,7 +982,8 @@ static int score_stream(const Form& f, const void* queries, const void* docs, in
     a.n_cand = n_cand;
     a.doc_offset = doc_offset;
     if (f.e4m3) a.score_scale = score_scale;
-    gpp::run_pick(a, st, f.e4m3);
+    if (f.biased) a.bias = f.bias;
+    gpp::run_pick(a, st, f.e4m3, f.biased);
   }
   // the bytes the pass streams: the shard once per query tile
   prof_end(f.e4m3 ? "rerank_fp8_stream_score" : "rerank_stream_score", st,
@@ -980,6 +1024,7 @@ static int rerank_run(const Form& f, const void* queries, const void* docs, int6
   if (Q == 0) return IRC_OK;
   IRC_REQUIRE(queries && cand_off && out_score && out_idx && out_n, "%s: null pointer", f.name);
   IRC_REQUIRE(n_cand == 0 || (cand && (N == 0 || docs)), "%s: null candidates / docs", f.name);
+  IRC_REQUIRE(!f.biased || n_cand == 0 || f.bias != nullptr, "%s: null bias", f.name);
   IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
               "%s: queries and docs must be 16-byte aligned", f.name);
   if (f.grouped) {
@@ -1070,6 +1115,23 @@ extern "C" int irc_rerank_topk_grouped(const void* queries, const void* docs, in
                                        irc_stream_t stream) {
   return rerank_run({"rerank_topk_grouped", (flags & IRC_RERANK_STREAM) != 0,
                      (flags & IRC_RERANK_E4M3) != 0, true, group_off, n_groups},
+                    queries, docs, Q, N, D, cand, cand_off, n_cand, k, doc_offset, score_scale,
+                    workspace, workspace_bytes, out_score, out_idx, out_n, stream);
+}
+
+// The candidate top-k by score + bias[i], over any of the four scoring passes (flags), per row
+// (group_off null) or per group: the addition happens in the scoring pass, before the collapse.
+extern "C" int irc_rerank_biased_topk(const void* queries, const void* docs, int64_t Q,
+                                      int64_t N, int64_t D, const int32_t* cand,
+                                      const int64_t* cand_off, int64_t n_cand, int64_t k,
+                                      int64_t doc_offset, const int64_t* group_off,
+                                      int64_t n_groups, uint32_t flags, float score_scale,
+                                      const float* bias, void* workspace,
+                                      int64_t workspace_bytes, float* out_score,
+                                      int64_t* out_idx, int32_t* out_n, irc_stream_t stream) {
+  return rerank_run({"rerank_topk_biased", (flags & IRC_RERANK_STREAM) != 0,
+                     (flags & IRC_RERANK_E4M3) != 0, group_off != nullptr, group_off, n_groups,
+                     true, bias},
                     queries, docs, Q, N, D, cand, cand_off, n_cand, k, doc_offset, score_scale,
                     workspace, workspace_bytes, out_score, out_idx, out_n, stream);
 }

@@ -52,6 +52,8 @@ SIGNATURES = {
     "irc_rerank_topk_grouped_workspace": (I64, [I64, I64, I64]),
     "irc_rerank_topk_grouped": (I32, [P, P, I64, I64, I64, P, P, I64, I64, I64, P, I64, U32, F32,
                                       P, I64, P, P, P, P]),
+    "irc_rerank_biased_topk": (I32, [P, P, I64, I64, I64, P, P, I64, I64, I64, P, I64, U32, F32,
+                                     P, P, I64, P, P, P, P]),
     "irc_topk_merge_grouped_workspace": (I64, [I64, I64, I64]),
     "irc_topk_merge_grouped": (I32, [P, P, I64, I64, I64, I64, P, I64, P, I64, P, P, P, P]),
     "irc_scan_topk_grouped_workspace": (I64, [I64, I64, I64]),

@@ -298,16 +298,34 @@ def rerank_method(Q: int, N: int, D: int, n_cand: int, dtype: str = "bf16") -> s
     return "stream" if n_cand >= frac * N * Q else "gather"
 
 
-def _sort_lists(cand: torch.Tensor, cand_off: torch.Tensor) -> torch.Tensor:
+def _sort_lists(cand: torch.Tensor, cand_off: torch.Tensor, with_perm: bool = False):
     """Every list of the CSR pair ascending, in one device sort of (owner, id) pairs; no
-    host synchronisation.  cand int32 / int64 with values in [-2^31, 2^31)."""
+    host synchronisation.  cand int32 / int64 with values in [-2^31, 2^31).  With
+    ``with_perm`` also the permutation: ``(sorted, perm)`` with ``sorted[j]`` the id that
+    stood at flat place ``perm[j]``, so whatever travels with a candidate (its bias) is
+    ``x[perm]``."""
     n = cand.numel()
     Q = cand_off.numel() - 1
     lengths = cand_off[1:] - cand_off[:-1]
     owner = torch.repeat_interleave(torch.arange(Q, device=cand.device), lengths, output_size=n)
     key = (owner << 32) + (cand.to(torch.int64) + 2 ** 31)
-    key, _ = torch.sort(key)
-    return ((key & 0xFFFFFFFF) - 2 ** 31).to(torch.int32)
+    key, perm = torch.sort(key)
+    ids = ((key & 0xFFFFFFFF) - 2 ** 31).to(torch.int32)
+    return (ids, perm) if with_perm else ids
+
+
+def _check_bias(bias, cand, queries):
+    """The ``bias`` argument of the rerank calls, checked before anything touches the device:
+    fp32, one entry per candidate, on the queries' device."""
+    if bias is None:
+        return
+    if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
+        raise TypeError("bias must be a float32 tensor, not "
+                        f"{getattr(bias, 'dtype', type(bias))}")
+    if bias.numel() != cand.numel():
+        raise ValueError(f"bias has {bias.numel()} entries for {cand.numel()} candidates")
+    if bias.device != queries.device:
+        raise ValueError(f"bias is on {bias.device}, the queries on {queries.device}")
 
 
 RERANK_FLAG_STREAM = 1  # irc.h: IRC_RERANK_STREAM
@@ -417,7 +435,7 @@ def local_group_slice(group_off: torch.Tensor, doc_offset: int, N: int):
 
 def rerank_topk(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
                 cand_off: torch.Tensor, k: int, doc_offset: int = 0, ws_tag: str = "rerank",
-                method: str = "gather", ascending: bool = False, group_off=None):
+                method: str = "gather", ascending: bool = False, group_off=None, bias=None):
     """Exact top-k of each query over ITS OWN candidate docs (sparse filter, dense rerank:
     src/evaluation.py:57-83 feeding :110-112).
 
@@ -452,17 +470,29 @@ def rerank_topk(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
     ascending lists under both methods, so without ``ascending=True`` the lists are sorted
     first under "gather" too.  It happens inside this one shard; the grouped results of
     several shards merge with ``topk_merge_grouped``, which keeps one row of a group whose
-    rows lie in two shards.  With ``group_off=None`` nothing changes."""
+    rows lie in two shards.  With ``group_off=None`` nothing changes.
+
+    ``bias`` (fp32, ``cand.numel()`` entries on the queries' device, parallel to ``cand``):
+    the fused score of hybrid retrieval (irc_rerank_biased_topk).  Candidate i is ranked by,
+    and returned with, ``score_i + bias[i]`` -- one fp32 addition to exactly the score the
+    call without ``bias`` computes under the same method; any weight is the caller's to
+    multiply in.  ``bias[i]`` belongs to the i-th entry of ``cand`` as passed, eligible or
+    not: it follows its candidate through the sort of unsorted lists.  With ``group_off``
+    the bias is added before the collapse, so a group is represented by the row with the
+    best fused score.  The values are not checked: a non-finite sum ranks as the keys order
+    it (+inf first, -inf after every finite value, NaN last).  ``bias=None`` is the call as
+    it was."""
     if method not in RERANK_METHODS:
         raise ValueError(f"method must be one of {RERANK_METHODS}, not {method!r}")
     _check_group_off(group_off, queries)
+    _check_bias(bias, cand, queries)
     require_hip(queries, docs, cand, cand_off)
     q = contig(queries, torch.bfloat16)
     d = contig(docs, torch.bfloat16)
     if d.shape[1] != q.shape[1]:
         raise ValueError(f"dim mismatch: queries D={q.shape[1]}, docs D={d.shape[1]}")
     return _rerank_call(q, d, cand, cand_off, k, doc_offset, 1.0, ws_tag, method, ascending,
-                        group_off)
+                        group_off, bias)
 
 
 # (method, e4m3 operands) -> the ungrouped native entry and the grouped entry's flags word
@@ -475,11 +505,14 @@ _RERANK_FORMS = {
 
 
 def _rerank_call(q, d, cand, cand_off, k, doc_offset, score_scale, ws_tag, method, ascending,
-                 group_off=None):
+                 group_off=None, bias=None):
     """The part of ``rerank_topk`` and ``rerank_topk_fp8`` after their operand checks: the
     id handling, the sort under "stream", the outputs and the native call.  The operands'
     dtype (uint8: e4m3 codes) and ``method`` choose the entry, or with ``group_off`` the
-    flags word of the one grouped entry; ``score_scale`` counts for e4m3 operands only."""
+    flags word of the one grouped entry; ``score_scale`` counts for e4m3 operands only.
+    With ``bias`` the one biased entry runs, by the same flags word, grouped or not; the
+    clamp / -1 replacement of int64 ids moves no candidate, and the sort's permutation is
+    applied to the bias."""
     Q, D = q.shape
     N = d.shape[0]
     grouped = group_off is not None
@@ -497,13 +530,30 @@ def _rerank_call(q, d, cand, cand_off, k, doc_offset, score_scale, ws_tag, metho
         else:
             cand = torch.where((cand < 0) | (cand >= 2 ** 31), cand.new_full((), -1), cand)
     off = contig(cand_off, torch.int64)
-    if ordered and not ascending:
+    if bias is not None:
+        bias = bias.reshape(-1)
+        if ordered and not ascending:
+            cand, perm = _sort_lists(cand.reshape(-1), off, with_perm=True)
+            bias = bias[perm]
+    elif ordered and not ascending:
         cand = _sort_lists(cand.reshape(-1), off)
     c = contig(cand, torch.int32)
     n_cand = c.numel()
     out_s = torch.empty((Q, k), dtype=torch.float32, device=q.device)
     out_i = torch.empty((Q, k), dtype=torch.int64, device=q.device)
     out_n = torch.empty((Q,), dtype=torch.int32, device=q.device)
+    if bias is not None:
+        b = contig(bias, torch.float32)
+        go = group_off.contiguous() if grouped else None
+        ws_fn = "irc_rerank_topk_grouped_workspace" if grouped else "irc_rerank_topk_workspace"
+        ws = workspace(int(_lib.fn(ws_fn)(Q, n_cand, k)), q.device, ws_tag)
+        _lib.call("irc_rerank_biased_topk", ptr(q), ptr(d), Q, N, D, ptr(c), ptr(off), n_cand,
+                  k, doc_offset, ptr(go) if grouped else None, go.numel() - 1 if grouped else 0,
+                  flags, score_scale, ptr(b), ptr(ws), ws.numel(), ptr(out_s), ptr(out_i),
+                  ptr(out_n), stream_ptr(q.device))
+        if grouped:
+            return out_s, out_i, out_n, _groups_of(go, out_i)
+        return out_s, out_i, out_n
     if not grouped:  # 8 bytes of workspace per candidate, against 24 for the grouped entry
         nbytes = int(_lib.fn("irc_rerank_topk_workspace")(Q, n_cand, k))
         ws = workspace(nbytes, q.device, ws_tag)
@@ -524,29 +574,38 @@ def _rerank_call(q, d, cand, cand_off, k, doc_offset, score_scale, ws_tag, metho
 def rerank_topk_fp8(queries: torch.Tensor, docs: torch.Tensor, cand: torch.Tensor,
                     cand_off: torch.Tensor, k: int, doc_offset: int = 0,
                     score_scale: float = 1.0, ws_tag: str = "rerank", method: str = "gather",
-                    ascending: bool = False, group_off=None):
+                    ascending: bool = False, group_off=None, bias=None):
     """``rerank_topk`` over e4m3 operands: queries [Q, D] and docs [N, D] are uint8 codes
     (``quantize_fp8``).  The scores are the fp32 dot products of the decoded values times
     ``score_scale`` (a power of two), as ``scan_topk_fp8`` reports them; candidates, ids,
-    ``method``, ``ascending``, ``group_off`` and the outputs are ``rerank_topk``'s.  "gather"
+    ``method``, ``ascending``, ``group_off``, ``bias`` and the outputs are ``rerank_topk``'s
+    (the bias is added to the score AFTER ``score_scale``).  "gather"
     is irc_rerank_topk_fp8, "stream" irc_rerank_topk_stream_fp8 (D % 128 == 0); on values
     whose sums are exact in fp32 the two agree bitwise."""
     if method not in RERANK_METHODS:
         raise ValueError(f"method must be one of {RERANK_METHODS}, not {method!r}")
     _check_group_off(group_off, queries)
+    _check_bias(bias, cand, queries)
     _require_e4m3(queries, docs)  # a wrong dtype is a TypeError on any device
     q, d = _fp8_operands(queries, docs)
     require_hip(cand, cand_off)
     return _rerank_call(q, d, cand, cand_off, k, doc_offset, float(score_scale), ws_tag, method,
-                        ascending, group_off)
+                        ascending, group_off, bias)
 
 
-def expand_ranges(cand: torch.Tensor, cand_off: torch.Tensor, row_off: torch.Tensor):
+def expand_ranges(cand: torch.Tensor, cand_off: torch.Tensor, row_off: torch.Tensor,
+                  values=None):
     """Candidate columns -> candidate rows: each candidate c of the CSR pair (cand,
     cand_off) becomes the row range [row_off[c], row_off[c + 1]) (empty ranges vanish) and
     the offsets are rebuilt.  Returns (rows int64, rows_off int64 [Q + 1]); lists that
     were ascending and unique stay so (row_off is non-decreasing).  Pure torch on the
-    tensors' device; the one host synchronisation is the total row count."""
+    tensors' device; the one host synchronisation is the total row count.
+
+    ``values`` ([n_cand], any dtype, parallel to ``cand``): a third result, ``values`` of
+    each row's candidate -- every row carries its page's value (the ``bias`` of
+    ``rerank_topk`` over the rows).  Without it the return is the pair."""
+    if values is not None and values.numel() != cand.numel():
+        raise ValueError(f"values has {values.numel()} entries for {cand.numel()} candidates")
     c = cand.to(torch.int64)
     off = cand_off.to(torch.int64)
     ro = row_off.to(device=c.device, dtype=torch.int64)
@@ -559,6 +618,8 @@ def expand_ranges(cand: torch.Tensor, cand_off: torch.Tensor, row_off: torch.Ten
     owner = torch.repeat_interleave(torch.arange(c.numel(), device=c.device), length,
                                     output_size=total)
     rows = start[owner] + (torch.arange(total, device=c.device) - (ends - length)[owner])
+    if values is not None:
+        return rows, rows_off, values.reshape(-1).to(c.device)[owner]
     return rows, rows_off
 
 
@@ -938,7 +999,8 @@ class ShardedDenseIndex:
 
     def search_candidates(self, queries: torch.Tensor, cand: torch.Tensor,
                           cand_off: torch.Tensor, k: int, ws_tag: str = "rerank",
-                          method: str = "gather", ascending: bool = False, group_off=None):
+                          method: str = "gather", ascending: bool = False, group_off=None,
+                          bias=None):
         """Top-k of each query over its own candidate docs only (global ids, the CSR pair
         ``SparseIndex.candidates`` / ``expand_ranges`` leave on the device): (scores
         [Q, k], idx [Q, k], n [Q]) as ``rerank_topk``.  bf16 and fp8 shards (on an fp8 index
@@ -972,6 +1034,13 @@ class ShardedDenseIndex:
         as ``rerank_topk`` documents it; "auto" chooses as without it.  Over a process
         group the result is the grouped top-k of the whole corpus: merging the per-shard
         grouped lists is exact ("Across shards").
+
+        ``bias`` (fp32, one entry per candidate, parallel to ``cand``, on the queries'
+        device): the candidates are ranked by score + bias as ``rerank_topk`` documents it
+        (on an fp8 index the bias is added to the descaled score).  Over a process group
+        each rank passes the bias of its own candidates and it is all-gathered with their
+        ids, in rank order; every rank passes one or none does.  Its checks (dtype, length,
+        device) run before the first collective like the others.
 
         Cost model: "gather" reads the candidate rows whole, once per
         (query, candidate), with no reuse across queries -- n_cand * D * 2 bytes -- while
@@ -1007,25 +1076,30 @@ class ShardedDenseIndex:
         row bytes from 160k candidates up (lists of one call that overlap hit the caches)
         and is latency-bound below."""
         _check_group_off(group_off, queries)
+        _check_bias(bias, cand, queries)
         if self.dtype == "fp8" and self.docs.dtype != torch.uint8:
             # before anything touches the queries or the device: a hand-built index or a
             # damaged header on load()
             raise ValueError("fp8 index: the shard is not e4m3 bytes (torch.uint8) but "
                              f"{self.docs.dtype}")
+        # the bias is passed on, and comes back, only when one was given
+        kw = {} if bias is None else {"bias": bias}
         if not self._sharded():
             return self._local_candidates(queries, cand, cand_off, k, ws_tag, method, ascending,
-                                          group_off)
-        c, off = self._own_candidates(queries, cand, cand_off, method)  # raises before (1)
-        allq, allc, alloff = self._gather_candidates(queries, c, off)  # (1)
-        out = self._local_candidates(allq, allc, alloff, k, ws_tag, method, ascending,
-                                     group_off)  # (2)
+                                          group_off, **kw)
+        own = self._own_candidates(queries, cand, cand_off, method, **kw)  # raises before (1)
+        gathered = self._gather_candidates(queries, *own)  # (1)
+        if bias is not None:
+            kw = {"bias": gathered[3]}
+        out = self._local_candidates(*gathered[:3], k, ws_tag, method, ascending, group_off,
+                                     **kw)  # (2)
         return self._exchange_merge_candidates(out[0], out[1], k, group_off)  # (3)
 
     # The steps of a sharded search_candidates are methods as search()'s are, so the
     # collective orchestration runs on CPU (gloo) with test doubles for the device calls
     # (tests/test_rerank_sharded_cpu.py): _local_candidates, _merge, _merge_grouped.
     def _local_candidates(self, queries, cand, cand_off, k, ws_tag="rerank", method="gather",
-                          ascending=False, group_off=None):
+                          ascending=False, group_off=None, bias=None):
         """This shard's candidate top-k: the whole of a single-process search_candidates,
         step (2) of a sharded one."""
         if method == "auto":
@@ -1037,18 +1111,19 @@ class ShardedDenseIndex:
             q8 = quantize_fp8(queries, self.fp8_scale)
             return rerank_topk_fp8(q8, self.docs, cand, cand_off, k, self.doc_offset,
                                    1.0 / (self.fp8_scale * self.fp8_scale), ws_tag=ws_tag,
-                                   method=method, ascending=ascending, group_off=group_off)
+                                   method=method, ascending=ascending, group_off=group_off,
+                                   bias=bias)
         return rerank_topk(queries, self.docs, cand, cand_off, k, self.doc_offset, ws_tag=ws_tag,
-                           method=method, ascending=ascending, group_off=group_off)
+                           method=method, ascending=ascending, group_off=group_off, bias=bias)
 
     def _merge_grouped(self, scores, idx, k, group_off):
         return topk_merge_grouped(scores, idx, k, group_off)
 
-    def _own_candidates(self, queries, cand, cand_off, method):
+    def _own_candidates(self, queries, cand, cand_off, method, bias=None):
         """This rank's arguments checked as the local call would check them, before any
         collective; returns the ids as flat int32 (an int64 id outside int32 is in no shard
         and is clamped to -1 / 2^31 - 1, which keeps an ascending list ascending) and the
-        offsets as int64."""
+        offsets as int64 -- and, when a ``bias`` was given, that as flat fp32 after them."""
         if method != "auto" and method not in RERANK_METHODS:
             raise ValueError(f"method must be 'auto' or one of {RERANK_METHODS}, not {method!r}")
         if queries.dim() != 2 or queries.shape[1] != self.docs.shape[1]:
@@ -1061,14 +1136,19 @@ class ShardedDenseIndex:
                              "queries (Q + 1)")
         if cand.dtype == torch.int64:
             cand = cand.clamp(-1, 2 ** 31 - 1)
-        return (cand.reshape(-1).to(torch.int32).contiguous(),
-                cand_off.reshape(-1).to(torch.int64).contiguous())
+        own =(cand.reshape(-1).to(torch.int32).contiguous(),
+               cand_off.reshape(-1).to(torch.int64).contiguous())
+        if bias is not None:
+            own += (bias.reshape(-1).contiguous(),)
+        return own
 
-    def _gather_candidates(self, queries, cand, cand_off):
+    def _gather_candidates(self, queries, cand, cand_off, bias=None):
         """(1) every rank's query slice and candidate lists, all-gathered in rank order:
         (queries [Q_all, D], cand int32 [n_all], cand_off int64 [Q_all + 1]).  One count
         exchange (a host sync) carries each rank's (queries, candidates); the offsets are
-        rebuilt from the gathered list lengths."""
+        rebuilt from the gathered list lengths.  With ``bias`` (fp32, parallel to ``cand``)
+        a fourth result: the ranks' biases gathered as the ids are, so entry j of it still
+        belongs to gathered candidate j."""
         import torch.distributed as dist
 
         world = dist.get_world_size(self.group)
@@ -1082,6 +1162,8 @@ class ShardedDenseIndex:
         allc = self._gather_ragged(cand, nc)
         lengths = self._gather_ragged(cand_off[1:] - cand_off[:-1], nq)
         alloff = torch.cat([lengths.new_zeros(1), torch.cumsum(lengths, 0)])
+        if bias is not None:
+            return allq, allc, alloff, self._gather_ragged(bias, nc)
         return allq, allc, alloff
 
     def _gather_ragged(self, x, counts):

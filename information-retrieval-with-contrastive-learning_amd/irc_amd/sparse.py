@@ -254,6 +254,44 @@ class SparseIndex:
     def closest_docs(self, query: str, k: int = 1):
         return self.batch_closest_docs([query], k)[0]
 
+    # the dense fp64 score rows of one chunk of queries in candidate_scores stay under this
+    MAX_DENSE_BYTES = 1 << 30
+
+    def candidate_scores(self, rows, weights, cand, cand_off):
+        """sum_r w_r * A[r, c] of each query at each of ITS OWN candidates c: fp64
+        [n_cand] on the device, parallel to ``cand`` (the CSR pair ``candidates`` leaves
+        there: query q owns cand[cand_off[q]:cand_off[q + 1]]; ids in [0, n_docs)) -- the
+        scores ``topk_rows`` ranks, bit for bit (irc_csr_spmv_f64 into zeroed dense rows,
+        gathered at (owner, candidate)), 0.0 where no row of the query reaches the
+        candidate.  No host copy of a result and no host synchronisation; the queries go
+        in chunks whose dense rows, chunk * n_docs * 8 bytes, stay under
+        ``MAX_DENSE_BYTES`` (at least one query per chunk)."""
+        Q = len(rows)
+        if cand_off.numel() != Q + 1:
+            raise ValueError(f"cand_off has {cand_off.numel()} entries for {Q} queries (Q + 1)")
+        c = cand.reshape(-1).to(torch.int64)
+        off = cand_off.reshape(-1).to(torch.int64)
+        n = c.numel()
+        out = torch.empty((n,), dtype=torch.float64, device=self.device)
+        if Q == 0 or n == 0:
+            return out
+        owner = torch.repeat_interleave(torch.arange(Q, device=self.device), off[1:] - off[:-1],
+                                        output_size=n)
+        chunk = max(1, self.MAX_DENSE_BYTES // (8 * max(self.n_docs, 1)))
+        st = stream_ptr(self.device)
+        for lo in range(0, Q, chunk):
+            hi = min(Q, lo + chunk)
+            t_off, t_rows, t_w, _ = self._pack(rows[lo:hi], weights[lo:hi])
+            dense = torch.zeros((hi - lo, self.n_docs), dtype=torch.float64, device=self.device)
+            _lib.call("irc_csr_spmv_f64", ptr(self.indptr), ptr(self.indices), ptr(self.data),
+                      self.n_docs, ptr(t_off), ptr(t_rows), ptr(t_w), hi - lo, ptr(dense), st)
+            # the chunk's candidates, by mask: their number is never read on the host
+            mine = (owner >= lo) & (owner < hi)
+            got = dense.reshape(-1)[((owner - lo).clamp(0, hi - lo - 1) * self.n_docs + c)
+                                    .clamp(0, dense.numel() - 1)]
+            out = torch.where(mine, got, out) if lo else got
+        return out
+
 
 def load_sparse_csr(filename):
     """utils.py:33-37: (csr matrix, metadata dict) from a build_tfidf .npz.  The

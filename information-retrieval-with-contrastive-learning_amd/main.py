@@ -5,6 +5,7 @@
                    [--seed 1337] [--logdir log] [--ckptdir ckpt] [--retrieval sparse|dense|hybrid]
                    [--rerank-method auto|gather|stream] [--rerank-unit line|page]
                    [--index-dtype bf16|fp8] [--index flat|ivf] [--nlist N] [--nprobe P]
+                   [--fusion-weight W]
 
 Multi-GPU (one process per GPU):
     torchrun --nproc-per-node N --master-addr 127.0.0.1 main.py [same flags]
@@ -20,7 +21,8 @@ the reference's sparse candidate filter per claim (default) or, with
 ``--retrieval dense``, the bi-encoder's exact top-k over the evidence corpus, or, with
 ``--retrieval hybrid``, that top-k over each claim's filter candidates only (the
 reference's two stages joined).  With either of the two, ``--rerank-unit page`` ranks the
-k best pages, each by its best line, instead of the k best lines.  The compute runs on the
+k best pages, each by its best line, instead of the k best lines.  ``--fusion-weight W``
+(hybrid only) ranks by the fused score dense + W * the claim's max-normalised TF-IDF page score.
 ``--index ivf`` (dense only) clusters the evidence corpus into ``--nlist`` lists and scores
 only the ``--nprobe`` lists nearest to each claim -- exactly, so what it trades for speed is
 which lists are looked at.  The compute runs on the MI355X HIP kernels only:
@@ -93,7 +95,19 @@ def get_args(argv=None):
                    help="--index ivf: lists the corpus (each rank's slice) is clustered into")
     p.add_argument("--nprobe", default=8, type=int,
                    help="--index ivf: lists probed per claim (per shard), 1 .. min(nlist, 1024)")
+    p.add_argument("--fusion-weight", default=0.0, type=float,
+                   help="--retrieval hybrid: rank each candidate line by dense + W * sparse, "
+                        "sparse being the claim's TF-IDF score of the line's page divided by "
+                        "the claim's largest (in [0, 1]), added on the device inside the "
+                        "candidate top-k. 0 (default): the dense score alone. Works with every "
+                        "--rerank-method, --rerank-unit page, --index-dtype fp8 and under "
+                        "torchrun")
     args = p.parse_args(argv)
+    if not args.fusion_weight >= 0 or args.fusion_weight == float("inf"):
+        p.error(f"--fusion-weight must be a finite number >= 0, not {args.fusion_weight}")
+    if args.fusion_weight > 0 and args.retrieval != "hybrid":
+        p.error("--fusion-weight fuses the sparse filter's score into the dense rerank: it "
+                "goes with --retrieval hybrid only")
     if args.index == "ivf":
         if args.retrieval == "hybrid":
             p.error("--index ivf ranks the probed lists, not a candidate filter's rows: it "

@@ -198,7 +198,8 @@ def hybrid_corpus(wiki, doc_ids):
 
 @torch.no_grad()
 def hybrid_search(model, dense_index, sparse_index, row_off, claims, k, device,
-                  bigram_only=False, method="gather", group_off=None):
+                  bigram_only=False, method="gather", group_off=None, fusion=0.0,
+                  tfidf_index=None):
     """Sparse filter, dense rerank for a batch of claims (src/evaluation.py:57-83 feeding
     :110-112), all on the device: the claims' candidate columns (SparseIndex.candidates)
     expanded to their evidence rows (``row_off``, int64 [n_cols + 1] on the device) and
@@ -212,21 +213,63 @@ def hybrid_search(model, dense_index, sparse_index, row_off, claims, k, device,
     Over a sharded ``dense_index`` (one with a process group) the call is collective:
     ``claims`` is this rank's slice of the batch (may be empty), ``row_off`` / ``group_off``
     stay in global row ids, and the result covers the whole batch, in rank order
-    (``ShardedDenseIndex.search_candidates``)."""
+    (``ShardedDenseIndex.search_candidates``).
+
+    ``fusion`` > 0 with a ``tfidf_index`` (a ``SparseIndex`` over the TF-IDF matrix with its
+    ``doc_freqs``, as ``TfidfDocRanker`` builds one): the rows are ranked by the FUSED score
+    dense + fusion * sparse, where sparse is the claim's TF-IDF score of the row's page
+    (``text2spvec`` query vector, ``SparseIndex.candidate_scores`` at the filter's
+    candidates) divided by the claim's largest such score -- in [0, 1]; all zeros when that
+    maximum is 0 -- cast to fp32 and multiplied by ``fusion`` in fp32.  Every row of a page
+    carries the page's value (``expand_ranges(values=)``), which ``search_candidates`` adds
+    as its ``bias``.  The returned scores are the fused ones.  ``fusion == 0``: no bias is
+    built and the call is the one above."""
     from irc_amd.retrieval import expand_ranges
 
+    if fusion < 0:
+        raise ValueError(f"fusion must be >= 0, not {fusion}")
+    fused = fusion > 0
+    if fused and tfidf_index is None:
+        raise ValueError("fusion > 0 needs the TF-IDF index (tfidf_index)")
+    bias = None
     if claims:
         q = model.ctx2vec(claims, device)
         cand, off = sparse_index.candidates(claims, bigram_only)
-        rows, rows_off = expand_ranges(cand, off, row_off)
+        if fused:
+            vecs = [tfidf_index.text2spvec(c) for c in claims]
+            page = tfidf_index.candidate_scores([v[0] for v in vecs], [v[1] for v in vecs],
+                                                cand, off)
+            rows, rows_off, bias = expand_ranges(cand, off, row_off,
+                                                 values=fusion_bias(page, off, fusion))
+        else:
+            rows, rows_off = expand_ranges(cand, off, row_off)
     else:  # a rank with no claim of this batch still joins the collectives
         q = torch.empty((0, dense_index.docs.shape[1]), dtype=torch.float32, device=device)
         rows = torch.empty(0, dtype=torch.int64, device=device)
         rows_off = torch.zeros(1, dtype=torch.int64, device=device)
-    if group_off is None:
-        return dense_index.search_candidates(q, rows, rows_off, k, method=method, ascending=True)
+        if fused:
+            bias = torch.empty(0, dtype=torch.float32, device=device)
+    kw = {} if group_off is None else {"group_off": group_off}
+    if fused:
+        kw["bias"] = bias
     return dense_index.search_candidates(q, rows, rows_off, k, method=method, ascending=True,
-                                         group_off=group_off)
+                                         **kw)
+
+
+def fusion_bias(page_scores, cand_off, fusion):
+    """The per-candidate prior of the fused score: fp64 ``page_scores`` [n_cand] (CSR offsets
+    ``cand_off`` int64 [Q + 1]) divided by each query's largest one -- 0 where that maximum
+    is not positive --, cast to fp32, times ``fusion`` in fp32.  Pure torch on the tensors'
+    device, no host synchronisation."""
+    n = page_scores.numel()
+    Q = cand_off.numel() - 1
+    owner = torch.repeat_interleave(torch.arange(Q, device=page_scores.device),
+                                    cand_off[1:] - cand_off[:-1], output_size=n)
+    top = torch.zeros(Q, dtype=torch.float64, device=page_scores.device)
+    top = top.scatter_reduce(0, owner, page_scores, "amax", include_self=True)[owner]
+    norm = torch.where(top > 0, page_scores / top, torch.zeros_like(page_scores))
+    return norm.to(torch.float32) * torch.tensor(fusion, dtype=torch.float32,
+                                                 device=page_scores.device)
 
 
 @torch.no_grad()
@@ -237,6 +280,9 @@ def predict_hybrid(args, k=100):
     recall@k.  ``args.rerank_method`` (default "auto") picks the scoring method per batch;
     the ranking contract is the same either way.  ``args.index_dtype`` (default "bf16"):
     "fp8" keeps the corpus as e4m3 bytes and ranks the quantised embeddings.
+    ``args.fusion_weight`` (main.py --fusion-weight, default 0): above 0 the rows are ranked
+    by dense + weight * (the claim's max-normalised TF-IDF page score), ``hybrid_search``'s
+    fused score, over the TF-IDF matrix this function opens for its metadata.
 
     Under data parallelism (``args.dist_group``, main.py under torchrun) the corpus is
     sharded as in ``predict_dense``: rank r encodes and keeps only its contiguous slice of
@@ -255,11 +301,14 @@ def predict_hybrid(args, k=100):
     model = model.to(args.device).eval()
     loader = get_dataloader(args, train=False, distributed=False)
     ds = args.config["dataset"]
-    _, metadata = load_sparse_csr(ds["tfidf"])
+    tfidf, metadata = load_sparse_csr(ds["tfidf"])
     count_matrix, _ = load_sparse_csr(ds["inverted_file"])
     if metadata.get("tokenizer", "simple") != "simple":
         raise ValueError("only the DrQA 'simple' tokenizer is supported on this path")
     sparse_index = SparseIndex(count_matrix, ngram=metadata["ngram"], device=args.device)
+    fusion = float(getattr(args, "fusion_weight", 0.0))  # main.py --fusion-weight
+    tfidf_index = SparseIndex(tfidf, ngram=metadata["ngram"], doc_freqs_=metadata["doc_freqs"],
+                              device=args.device) if fusion > 0 else None
     titles, texts, row_off = hybrid_corpus(loader.dataset.wiki, metadata["doc_dict"][1])
     row_off = torch.tensor(row_off, dtype=torch.int64, device=args.device)
     lo, hi = shard_bounds(len(texts), world, rank)
@@ -276,8 +325,9 @@ def predict_hybrid(args, k=100):
         s = time.time()
         c0, c1 = shard_bounds(len(claims), world, rank)
         # rows: the whole batch, in order
+        fuse = {"fusion": fusion, "tfidf_index": tfidf_index} if fusion > 0 else {}
         idx = hybrid_search(model, index, sparse_index, row_off, claims[c0:c1], k, args.device,
-                            method=method, group_off=row_off if by_page else None)[1]
+                            method=method, group_off=row_off if by_page else None, **fuse)[1]
         torch.cuda.synchronize()
         if rank == 0:
             print(f"batch of {len(claims)} claims: {time.time() - s:.4f}s")
@@ -286,5 +336,7 @@ def predict_hybrid(args, k=100):
             hits += int(any(titles[j] in gold for j in row if j >= 0))
             total += 1
     if rank == 0:
-        print(f"evidence recall@{k}{' (pages)' if by_page else ''}: {hits / max(total, 1):.4f}")
+        unit = (" (pages)" if by_page else "") + (f" (fusion weight {fusion:g})" if fusion > 0
+                                                  else "")
+        print(f"evidence recall@{k}{unit}: {hits / max(total, 1):.4f}")
     return hits / max(total, 1)

@@ -10,6 +10,8 @@ cross.
     python tools/rerank_probe.py --tables profiles/rerank_group_probe.json
     python tools/rerank_probe.py --merge > profiles/rerank_merge_probe.json  # see below
     python tools/rerank_probe.py --tables profiles/rerank_merge_probe.json
+    python tools/rerank_probe.py --bias [--dtype fp8] [--grouped] [--parent-lib SO]  # see below
+    python tools/rerank_probe.py --tables profiles/rerank_bias_probe.json
 
 One MI355X, the C3 shard (250k x 768 bf16, larger than the Infinity Cache), random
 ascending candidate lists of 0.1 / 1 / 5 / 25 % of the shard per query, Q in {1, 16, 64,
@@ -44,6 +46,15 @@ profiled pass.  What the merge adds to a sharded search_candidates.
 best lines) and with the candidate route to the same pages, search_candidates(method="stream",
 group_off=...) over lists of ALL rows; profiles/scan_group_probe.json holds the bf16 and the
 fp8 run's lines under "bf16" and "fp8" (``--tables`` prints both).
+``--bias [--dtype fp8] [--grouped]``: the biased call (rerank_topk(bias=...), a fixed-seed
+fp32 bias per candidate) beside the unbiased call in the same cells and list draws, gathered
+and streamed, alternating window by window; with ``--grouped`` both carry the page map of
+``--grouped``.  ``--parent-lib SO`` (a libirc_hip.so built from the parent commit) adds the
+A/B of the unbiased calls: the same native entry of that library and of this tree's, called
+through ctypes on the same buffers, join the alternation (``parent_*`` / ``this_*``), and a
+cell is accepted when this tree's median is no higher than the parent's median plus the
+parent's own min-max window spread of that run (``ab_ok``).  profiles/rerank_bias_probe.json
+holds the runs' lines under "bf16", "fp8", "bf16_grouped", "fp8_grouped".
 Prints a table to stderr and ONE JSON line to stdout."""
 import argparse
 import ctypes
@@ -396,6 +407,181 @@ def scan_group_probe(args):
                       "cells": cells}))
 
 
+def bias_tables(r):
+    """The fused-score tables of DESIGN.md 6e from one --bias run: per cell the unbiased /
+    biased call and their ratio, gathered and streamed; with a parent library the A/B of the
+    unbiased native entries (parent median + its window spread against this tree's median)."""
+    qs = sorted({c["Q"] for c in r["cells"]})
+    fracs = sorted({c["frac"] for c in r["cells"]})
+    cell = {(c["Q"], c["frac"]): c for c in r["cells"]}
+    what = f"{r['dtype']}{', per group' if r.get('grouped') else ''}"
+    for m in ("gather", "stream"):
+        print(f"{m}, {what}: call us, unbiased / biased (ratio)")
+        print("    candidates per query " + "".join(f"{'Q = ' + str(q):>24}" for q in qs))
+        for f in fracs:
+            c0 = cell[qs[0], f]
+            line = f"    {c0['cand_per_query']:>8,} ({100 * f:g} %)".ljust(27)
+            for q in qs:
+                c = cell[q, f]
+                line += f"{c[m + '_call_us']:9,.0f} /{c[m + '_bias_call_us']:7,.0f} " \
+                        f"({c[m + '_bias_ratio']:.3f})"
+            print(line)
+    worst = max(r["cells"], key=lambda c: max(c["spread_pct"].values()))
+    print(f"largest min-max spread of a cell's windows: {max(worst['spread_pct'].values()):.2f}% "
+          f"(Q = {worst['Q']}, {100 * worst['frac']:g}%); rounds per cell: {r['rounds']}")
+    if not r.get("parent_lib"):
+        return
+    for m in ("gather", "stream"):
+        print(f"{m}, {what}: unbiased native entry, parent / this tree, us (+ parent's spread)")
+        for f in fracs:
+            line = f"    {cell[qs[0], f]['cand_per_query']:>8,} ({100 * f:g} %)".ljust(27)
+            for q in qs:
+                c = cell[q, f]
+                lo, hi = c[f"parent_{m}_call_us_minmax"]
+                line += f"{c['parent_' + m + '_call_us']:8,.1f} /{c['this_' + m + '_call_us']:8,.1f}" \
+                        f" (+{hi - lo:5.1f}){' ' if c['ab_ok'][m] else '!'}"
+            print(line)
+    bad = [(c["Q"], c["frac"], m) for c in r["cells"] for m in ("gather", "stream")
+           if not c["ab_ok"][m]]
+    print(f"cells above the parent's median + spread: {bad if bad else 'none'}")
+
+
+def bias_probe(args):
+    """--bias: the biased call next to the unbiased call on the same lists, gathered and
+    streamed (per group with --grouped), alternating window by window; with --parent-lib the
+    unbiased native entry of the parent's library and of this tree's join the alternation on
+    the same buffers.  ONE JSON line to stdout."""
+    from irc_amd import _lib, retrieval
+    from irc_amd._torch import ptr, stream_ptr
+
+    fp8 = args.dtype == "fp8"
+    lib = _lib.load()
+    parent = None
+    if args.parent_lib:
+        parent = ctypes.CDLL(args.parent_lib)
+        for name in ("irc_rerank_topk", "irc_rerank_topk_stream", "irc_rerank_topk_fp8",
+                     "irc_rerank_topk_stream_fp8", "irc_rerank_topk_grouped"):
+            getattr(parent, name).restype, getattr(parent, name).argtypes = _lib.SIGNATURES[name]
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(2025)
+    docs = torch.nn.functional.normalize(
+        torch.randn(args.n, args.d, generator=g)).bfloat16().to(dev)
+    torch.manual_seed(2025)
+    if fp8:
+        docs = retrieval.quantize_fp8(docs)
+    descale = 1.0 / (retrieval.FP8_SCALE * retrieval.FP8_SCALE) if fp8 else 1.0
+    group_off = None
+    if args.grouped:  # the page draw of --grouped
+        sizes = 1 + torch.empty(args.n, dtype=torch.float64).exponential_(1 / 9.5,
+                                                                          generator=g).long()
+        ends = torch.cumsum(sizes, 0)
+        ends = ends[: int((ends < args.n).sum())]
+        group_off = torch.cat([torch.zeros(1, dtype=torch.int64), ends,
+                               torch.tensor([args.n])]).to(dev)
+    n_groups = group_off.numel() - 1 if args.grouped else 0
+    ws_fn = "irc_rerank_topk_grouped_workspace" if args.grouped else "irc_rerank_topk_workspace"
+    cells = []
+    for Q in args.q:
+        qq = torch.nn.functional.normalize(
+            torch.randn(Q, args.d, generator=g)).bfloat16().to(dev)
+        if fp8:
+            qq = retrieval.quantize_fp8(qq)
+        out = (torch.empty((Q, args.k), dtype=torch.float32, device=dev),
+               torch.empty((Q, args.k), dtype=torch.int64, device=dev),
+               torch.empty((Q,), dtype=torch.int32, device=dev))
+        for frac in args.frac:
+            n = max(1, int(round(frac * args.n)))
+            cands = [torch.cat([torch.randperm(args.n, device=dev)[:n].sort().values
+                                for _ in range(Q)]).to(torch.int32) for _ in range(args.sets)]
+            biases = [torch.randn(Q * n, device=dev) * 0.1 for _ in range(args.sets)]
+            off = torch.arange(Q + 1, device=dev, dtype=torch.int64) * n
+            ws = torch.empty(int(_lib.fn(ws_fn)(Q, Q * n, args.k)), dtype=torch.uint8, device=dev)
+
+            def wrapped(method, biased):
+                counter = [0]
+
+                def call():
+                    counter[0] += 1
+                    c = cands[counter[0] % args.sets]
+                    b = biases[counter[0] % args.sets] if biased else None
+                    if fp8:
+                        return retrieval.rerank_topk_fp8(qq, docs, c, off, args.k, 0, descale,
+                                                         method=method, ascending=True,
+                                                         group_off=group_off, bias=b)
+                    return retrieval.rerank_topk(qq, docs, c, off, args.k, method=method,
+                                                 ascending=True, group_off=group_off, bias=b)
+                return call
+
+            def native(which, method):
+                """The unbiased native entry of one library, on this cell's buffers."""
+                counter = [0]
+                flags = (1 if method == "stream" else 0) | (2 if fp8 else 0)
+                if args.grouped:
+                    fn = which.irc_rerank_topk_grouped
+                    mid = (ptr(group_off), n_groups, flags, descale)
+                else:
+                    fn = getattr(which, "irc_rerank_topk" + ("_stream" if method == "stream"
+                                                             else "") + ("_fp8" if fp8 else ""))
+                    mid = (descale,) if fp8 else ()
+
+                def call():
+                    counter[0] += 1
+                    c = cands[counter[0] % args.sets]
+                    rc = fn(ptr(qq), ptr(docs), Q, args.n, args.d, ptr(c), ptr(off), Q * n, args.k,
+                            0, *mid, ptr(ws), ws.numel(), ptr(out[0]), ptr(out[1]), ptr(out[2]),
+                            stream_ptr(dev))
+                    if rc != 0:
+                        raise SystemExit(f"native rerank entry failed: rc={rc}")
+                return call
+
+            timed = [(f"{m}{s}", wrapped(m, b)) for m in ("gather", "stream")
+                     for s, b in (("", False), ("_bias", True))]
+            if parent is not None:
+                timed += [(f"{w}_{m}", native(which, m)) for m in ("gather", "stream")
+                          for w, which in (("parent", parent), ("this", lib))]
+            est = {}
+            for name, fn in timed:
+                for _ in range(3):
+                    fn()
+                torch.cuda.synchronize()
+                est[name] = _window_ms(fn, 5)
+            reps = {m: max(2 * args.sets, min(4000, int(args.window_ms / max(est[m], 1e-3))))
+                    for m in est}
+            for m in reps:
+                reps[m] -= reps[m] % args.sets  # every draw equally often
+            t = {m: [] for m, _ in timed}
+            for _ in range(args.rounds):  # alternate them window by window
+                for m, fn in timed:
+                    t[m].append(_window_ms(fn, reps[m]))
+            med = {m: statistics.median(t[m]) * 1e3 for m in t}
+            cell = {"Q": Q, "frac": frac, "cand_per_query": n, "n_cand": Q * n, "reps": reps,
+                    "spread_pct": {m: 100.0 * (max(t[m]) - min(t[m])) / statistics.median(t[m])
+                                   for m in t}}
+            for m in t:
+                cell[f"{m}_call_us"] = med[m]
+                cell[f"{m}_call_us_minmax"] = [min(t[m]) * 1e3, max(t[m]) * 1e3]
+            for m in ("gather", "stream"):
+                cell[f"{m}_bias_ratio"] = med[f"{m}_bias"] / med[m]
+            if parent is not None:
+                cell["ab_ok"] = {
+                    m: med[f"this_{m}"] <= med[f"parent_{m}"] +
+                    (max(t[f"parent_{m}"]) - min(t[f"parent_{m}"])) * 1e3
+                    for m in ("gather", "stream")}
+            cells.append(cell)
+            ab = "" if parent is None else (
+                f"  A/B gather {med['parent_gather']:.1f} / {med['this_gather']:.1f}"
+                f" stream {med['parent_stream']:.1f} / {med['this_stream']:.1f} {cell['ab_ok']}")
+            print(f"Q={Q:4d} frac={frac:6.3f} n_cand={Q * n:9d}  gather {med['gather']:9.1f} / "
+                  f"biased {med['gather_bias']:9.1f} us ({cell['gather_bias_ratio']:.3f})  stream "
+                  f"{med['stream']:9.1f} / biased {med['stream_bias']:9.1f} us "
+                  f"({cell['stream_bias_ratio']:.3f}){ab}", file=sys.stderr, flush=True)
+    print(json.dumps({"probe": "rerank_bias", "device": torch.cuda.get_device_name(0),
+                      "dtype": args.dtype, "grouped": bool(args.grouped),
+                      "parent_lib": bool(args.parent_lib), "N": args.n, "D": args.d, "k": args.k,
+                      "rounds": args.rounds, "window_ms": args.window_ms, "sets": args.sets,
+                      "cells": cells}))
+
+
 def merge_tables(r):
     """The table of DESIGN.md 6e "Across shards": per shape the two merges' call times and
     the grouped merge's kernels."""
@@ -509,6 +695,14 @@ def main():
             return grouped_tables(rec)
         if isinstance(rec, dict) and rec.get("probe") == "scan_grouped":
             return scan_group_tables(rec)
+        if isinstance(rec, dict) and rec.get("probe") == "rerank_bias":
+            return bias_tables(rec)
+        if isinstance(rec, dict) and rec.get("bf16", {}).get("probe") == "rerank_bias":
+            for key in ("bf16", "fp8", "bf16_grouped", "fp8_grouped"):
+                if key in rec:
+                    bias_tables(rec[key])
+                    print()
+            return None
         if isinstance(rec, dict) and "bf16" in rec and "fp8" in rec:  # the two runs of a probe
             show = scan_group_tables if rec["bf16"].get("probe") == "scan_grouped" else \
                 grouped_tables
@@ -535,10 +729,18 @@ def main():
     ap.add_argument("--scan-grouped", action="store_true",
                     help="time search(group_off=...) next to search and to the candidate "
                          "route over all-rows lists")
+    ap.add_argument("--bias", action="store_true",
+                    help="time rerank_topk(bias=...) next to the unbiased call (with --grouped: "
+                         "both per group)")
+    ap.add_argument("--parent-lib", type=str, default=None,
+                    help="--bias: a libirc_hip.so of the parent commit; its unbiased native "
+                         "entries join the alternation beside this tree's (the A/B)")
     args = ap.parse_args()
     fp8 = args.dtype == "fp8"
     if not torch.cuda.is_available():
         raise SystemExit("rerank_probe measures on a HIP device; none is visible")
+    if args.bias:
+        return bias_probe(args)
     if args.merge:
         return merge_probe(args)
     if args.scan_grouped:
