@@ -412,11 +412,27 @@ int irc_scan_scores(const void* queries, const void* docs, int64_t Q, int64_t N,
  * single-pass GEMM filter (Q in [q, 256]: the 4 largest keys of every (256-doc tile,
  * query) kept in the filter's epilogue, then an exact select over those lists that
  * rescans any tile whose 4th key reaches the k-th; no threshold sample pass).  q > 256
- * selects the sampled-threshold pipeline for every Q.  Same top-k either way (exact);
- * env IRC_SCAN_PPL_MINQ sets the initial value (default: off, 2^30), IRC_SCAN_PPL=0
- * turns it off.  Returns the previous value.  Replaces nothing in the reference: it selects
- * between two exact implementations of evaluation.py:110-112 / tfidf_doc_ranker.py:60-75. */
+ * selects the sampled-threshold pipeline for every Q.  Same top-k either way (exact).
+ * The default is off (2^30); it is set at run time only, by this call.  Returns the previous
+ * value.  Replaces nothing in the reference: it selects between two exact implementations
+ * of evaluation.py:110-112 / tfidf_doc_ranker.py:60-75. */
 int irc_scan_set_ppl_min_q(int q);
+
+/* Which passes irc_scan_topk (fp8 != 0: irc_scan_topk_fp8) runs for a shape under the
+ * current knobs (test / diagnostic aid; host arithmetic, no device access).  *chunk_docs =
+ * N, or the size of one doc chunk where the shard is scanned in chunks and merged;
+ * *sample, *filter describe the scan of one such chunk: the threshold pass over a strided
+ * sample, then the pass over every doc with its select.  Sizes are checked as the scan
+ * checks them. */
+#define IRC_SCAN_SAMPLE_NONE 0       /* no threshold pass */
+#define IRC_SCAN_SAMPLE_TILE 1       /* stationary-query kernel, group maxima, radix select */
+#define IRC_SCAN_SAMPLE_GEMM 2       /* GEMM kernel, 4 keys per (256-doc tile, query) */
+#define IRC_SCAN_FILTER_TILE_LISTS 0 /* single pass, stationary-query kernel, 4-key lists */
+#define IRC_SCAN_FILTER_GEMM_LISTS 1 /* single pass, GEMM kernel (irc_scan_set_ppl_min_q) */
+#define IRC_SCAN_FILTER_GEMM_KEYS 2  /* GEMM kernel, every key >= the threshold */
+#define IRC_SCAN_FILTER_TILE_KEYS 3  /* stationary-query kernel, every key >= the threshold */
+int irc_scan_topk_pipeline(int64_t Q, int64_t N, int64_t D, int64_t k, int fp8, int* sample,
+                           int* filter, int64_t* chunk_docs);
 
 /* fp8 (e4m3fn) corpus scan: the same exact top-k as irc_scan_topk over e4m3
  * queries [Q][D] and docs [N][D] (16-byte aligned rows), products exact, fp32

@@ -108,6 +108,23 @@ struct PArgs {
   int n_groups;
 };
 
+// The retrieval pass C[q][doc] = queries . docs^T: A = queries [Q][D], B = docs [N][D], both
+// dense and K-major; e4m3 operands are addressed in 2-byte units (K = D / 2).  Sets these
+// eight fields only: the caller adds what its epilogue reads.
+inline PArgs qd_pass(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,
+                     bool e4m3) {
+  PArgs a{};
+  a.A = static_cast<const unsigned short*>(queries);
+  a.B = static_cast<const unsigned short*>(docs);
+  a.M = (int)Q;
+  a.N = (int)N;
+  a.K = (int)(e4m3 ? D / 2 : D);
+  a.kchunk = a.K;
+  a.lda = a.K;
+  a.ldb = a.K;
+  return a;
+}
+
 int splits_for(int out_f32, int epi, int64_t M, int64_t N, int64_t K, int64_t batch,
                int64_t budget = 256);
 // compute units of the current device (cached per device; 0 if unknown)

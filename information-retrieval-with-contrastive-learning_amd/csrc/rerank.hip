@@ -967,15 +967,7 @@ static int score_stream(const Form& f, const void* queries, const void* docs, in
   hipLaunchKernelGGL(rerank_foreign_kernel, dim3((unsigned)Q, RF_Y), dim3(RF_NT), 0, st, cand,
                      cand_off, n_cand, doc_offset, N, keys);
   if (N > 0) {
-    gpp::PArgs a{};
-    a.A = static_cast<const unsigned short*>(queries);
-    a.B = static_cast<const unsigned short*>(docs);
-    a.M = (int)Q;
-    a.N = (int)N;
-    a.K = (int)(f.e4m3 ? D / 2 : D);  // 2-byte units
-    a.kchunk = a.K;
-    a.lda = a.K;
-    a.ldb = a.K;
+    gpp::PArgs a = gpp::qd_pass(queries, docs, Q, N, D, f.e4m3);
     a.keys = keys;
     a.cand = cand;
     a.cand_off = cand_off;
@@ -1192,15 +1184,7 @@ extern "C" int irc_scan_topk_grouped(const void* queries, const void* docs, int6
   if (n_keys > 0 && hipMemsetAsync(gmax, 0, (size_t)n_keys * 8, st) != hipSuccess)
     return check_launch("scan_group memset");
   if (N > 0 && n_groups > 0) {
-    gpp::PArgs a{};
-    a.A = static_cast<const unsigned short*>(queries);
-    a.B = static_cast<const unsigned short*>(docs);
-    a.M = (int)Q;
-    a.N = (int)N;
-    a.K = (int)(e4m3 ? D / 2 : D);  // 2-byte units
-    a.kchunk = a.K;
-    a.lda = a.K;
-    a.ldb = a.K;
+    gpp::PArgs a = gpp::qd_pass(queries, docs, Q, N, D, e4m3);
     a.doc_offset = doc_offset;
     if (e4m3) a.score_scale = score_scale;
     a.gmax = gmax;

@@ -23,29 +23,9 @@
 
 #include <atomic>
 #include <cmath>
+#include <type_traits>
 
 #include "gemm_pp.h"
-
-#ifndef IRC_SCAN_AUX
-#define IRC_SCAN_AUX 0  // cache policy of the corpus stream (0: default)
-#endif
-#ifndef IRC_SCAN_SEL_STOP
-#define IRC_SCAN_SEL_STOP -1  // diagnostic builds: the final select returns at stage N
-#endif
-// 1: the DMA of tile it + NBUF is issued into tile it's ring slot as soon as every
-// wave holds tile it's A fragments in registers (one extra barrier), so NBUF tiles
-// are in flight during the MFMAs and the epilogue instead of NBUF - 1 (0: the
-// round-2 order, the next DMA at the top of each iteration).
-#define IRC_SCAN_EARLY_ISSUE 1
-// 1: that DMA is issued piece by piece between the tile's MFMAs instead of all at once
-// ahead of them, so a piece whose issue waits on a full memory queue no longer holds the
-// MFMAs back.  C3 shard (250k x 768), filter: Q = 48 / 64 / 96 / 128 single pass
-// 92.6-95.4 / 92.9-93.1 / 108.6-109.0 / 111.0-111.7 -> 87.5-88.5 / 88.0-88.4 / 105.0-105.2 /
-// 108.1-108.6 us, the sampled pipeline at Q = 64 84.6 -> 79.5-79.9 us, Q <= 16 within
-// +-1 us (two interleaved runs, profiles/r06_e_*); same results (0: the all-at-once form).
-#ifndef IRC_SCAN_IL
-#define IRC_SCAN_IL 1
-#endif
 
 namespace irc {
 namespace scan {
@@ -204,7 +184,7 @@ void scan_tile_kernel(
       uint32_t off = goff[t];
       if (tail && tile * TD + grow[t] >= NS)  // clamp: loaded but never kept
         off -= (uint32_t)((tile * TD + grow[t] - (NS - 1)) * row_bytes);
-      glds16_pol<IRC_SCAN_AUX>(src0 + off, base + i * 1024);
+      glds16_pol<0>(src0 + off, base + i * 1024);
     }
   };
   auto issue_tile = [&](int tile, int buf) {
@@ -218,12 +198,15 @@ void scan_tile_kernel(
         uint32_t off = goff[t];
         if (tail && tile * TD + grow[t] >= NS)  // clamp: loaded but never kept
           off -= (uint32_t)((tile * TD + grow[t] - (NS - 1)) * row_bytes);
-        glds16_pol<IRC_SCAN_AUX>(src0 + off, base + i * 1024);
+        glds16_pol<0>(src0 + off, base + i * 1024);
       }
     }
   };
 
-  constexpr int PRE = IRC_SCAN_EARLY_ISSUE ? G::NBUF : G::NBUF - 1;  // tiles issued up front
+  // The DMA of tile it + NBUF goes into tile it's ring slot as soon as every wave holds
+  // tile it's A fragments in registers (one extra barrier), so NBUF tiles are in flight
+  // during the MFMAs and the epilogue.
+  constexpr int PRE = G::NBUF;  // tiles issued up front
 #pragma unroll
   for (int bb = 0; bb < PRE; ++bb)
     if (bb < my_tiles) issue_tile(t_begin + bb, bb);
@@ -271,8 +254,6 @@ void scan_tile_kernel(
 
   for (int it = 0; it < my_tiles; ++it) {
     const int tile = t_begin + it;
-    if (!IRC_SCAN_EARLY_ISSUE && it + G::NBUF - 1 < my_tiles)
-      issue_tile(tile + G::NBUF - 1, (it + G::NBUF - 1) % G::NBUF);
     const int after = my_tiles - 1 - it;
     const int ahead = after < G::NBUF - 1 ? after : G::NBUF - 1;
     // survivor stores younger than tile it's DMA: those of the iterations after
@@ -284,12 +265,6 @@ void scan_tile_kernel(
     wait_vmcnt_n(__builtin_amdgcn_readfirstlane(ahead == 0 ? 0 : ahead * PW + extra));
     wg_barrier();  // every wave's share of the tile has landed
 
-#ifdef IRC_SCAN_DMA_ONLY  // diagnostic build: the corpus stream alone
-    wg_barrier();
-    if (IRC_SCAN_EARLY_ISSUE && it + G::NBUF < my_tiles)
-      issue_tile(tile + G::NBUF, it % G::NBUF);
-    continue;
-#endif
     const char* tb = smem + (it % G::NBUF) * G::TILE_BYTES + kh * (D * EB / KS);
     f32x16 acc = (f32x16)0.0f;
     {
@@ -299,11 +274,8 @@ void scan_tile_kernel(
 #pragma unroll
       for (int c = 0; c < NCW; ++c)
         af[c] = *reinterpret_cast<const u16x8*>(tb + lo[c & 7] + 256 * (c >> 3));
-      if (IRC_SCAN_EARLY_ISSUE) {
-        // the slot is free once every wave's fragment reads have returned
-        lds_barrier();
-        if (!IRC_SCAN_IL && it + G::NBUF < my_tiles) issue_tile(tile + G::NBUF, it % G::NBUF);
-      }
+      // the slot is free once every wave's fragment reads have returned
+      lds_barrier();
 #pragma unroll
       for (int c = 0; c < NCW; ++c) {
         if constexpr (EB == 2) {
@@ -316,20 +288,19 @@ void scan_tile_kernel(
           acc = __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(a2[0], b2[0], acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(a2[1], b2[1], acc, 0, 0, 0);
         }
-        if (IRC_SCAN_IL && IRC_SCAN_EARLY_ISSUE && it + G::NBUF < my_tiles) {
+        if (it + G::NBUF < my_tiles) {
           // the next DMA spread over the MFMA chain: a piece whose issue stalls on a full
-          // memory queue then no longer holds back the MFMAs behind it
+          // memory queue then no longer holds back the MFMAs behind it.  Against the whole
+          // DMA issued ahead of the chain, C3 shard (250k x 768), filter: Q = 48 / 64 / 96 /
+          // 128 single pass 92.6-95.4 / 92.9-93.1 / 108.6-109.0 / 111.0-111.7 -> 87.5-88.5 /
+          // 88.0-88.4 / 105.0-105.2 / 108.1-108.6 us, the sampled pipeline at Q = 64 84.6 ->
+          // 79.5-79.9 us, Q <= 16 within +-1 us (two interleaved runs, profiles/r06_e_*).
 #pragma unroll
           for (int t = 0; t < PW; ++t)
             if (t * NCW / PW == c) issue_piece(tile + G::NBUF, it % G::NBUF, t);
         }
       }
     }
-#ifdef IRC_SCAN_MFMA_ONLY  // diagnostic build
-    if (acc[0] == 12345.f) myreg[0] = 1;  // keep the MFMAs alive
-    wg_barrier();
-    continue;
-#endif
     if (KS == 4) {
       // Butterfly reduce-scatter of the four k-slice partial sums: round 1 with
       // wave kh ^ 2 (keep half kh >> 1 of the 16 registers, send the other), round 2
@@ -395,11 +366,6 @@ void scan_tile_kernel(
       }
     }
 
-#ifdef IRC_SCAN_NO_EPI  // diagnostic build
-    if (acc[0] == 12345.f) myreg[0] = 1;
-    wg_barrier();
-    continue;
-#endif
     // Epilogue: C[doc row][query col]; col = lane&31, row = (j&3) + 8(j>>2) + 4h.
     // The wave finishes registers jj + joff of acc (joff: wave-uniform half).
     int nst = 0;
@@ -470,7 +436,7 @@ void scan_tile_kernel(
 #pragma unroll
       for (int jj = 0; jj < JPW; ++jj) pm |= (uint32_t)(!(fin[jj] < ltf)) << jj;
       while (__ballot(pm != 0)) {
-#if defined(IRC_SCAN_STAMPS) && !defined(IRC_SCAN_NO_ROUNDS)  // diagnostic: LTOP rounds (wave 0 of blocks < 256)
+#ifdef IRC_SCAN_STAMPS  // diagnostic: LTOP rounds (wave 0 of blocks < 256)
         if (wave == 0 && lane == 0 && blockIdx.x < 256)
           atomicAdd((unsigned long long*)&dbg_stamps[3][28], 1ull);
 #endif
@@ -512,18 +478,12 @@ void scan_tile_kernel(
         const int s = s0row + (j & 3) + 8 * (j >> 2) + 4 * h;
         const uint64_t key = make_key(v, idx_base + (uint32_t)s * (uint32_t)stride);
         const bool keep = cand && (q < Q) && (s < NS) && key >= qthr;
-#ifdef IRC_SCAN_NO_STORE  // diagnostic build: survivors counted, never stored
-        if (keep) ++nsurv;
-#else
         push(keep, key);
-#endif
       }
     }
     nst_hist = (nst_hist << 8) | (uint64_t)(nst < 255 ? nst : 255);
-    // all reads of this buffer (and of xbuf) done before reuse; with the early issue
-    // the slot was released above and the next iteration's two barriers precede any
-    // xbuf write
-    if (!IRC_SCAN_EARLY_ISSUE) wg_barrier();
+    // the ring slot was released above, and the next iteration's two barriers precede
+    // any xbuf write
   }
 
   if (MODE == LTOP) {
@@ -801,7 +761,6 @@ __device__ __forceinline__ void select_fast(const Src& src, int q, int k, int mo
   }
   __syncthreads();
   STAMP(mode, 2);
-  if (IRC_SCAN_SEL_STOP == 2 && mode == SEL_FINAL) return;
 
   uint64_t kth = 0;  // 0 = keep everything
   if (M > (uint32_t)k) {
@@ -881,7 +840,6 @@ __device__ __forceinline__ void select_fast(const Src& src, int q, int k, int mo
     return;
   }
   STAMP(mode, 12);
-  if (IRC_SCAN_SEL_STOP == 3 && mode == SEL_FINAL) return;
   // collect the exactly min(M, k) keys >= kth: one LDS atomic per wave (its U
   // ballots counted first; a returning atomic per slot serialised U round trips)
   {
@@ -906,7 +864,6 @@ __device__ __forceinline__ void select_fast(const Src& src, int q, int k, int mo
   }
   __syncthreads();
   STAMP(mode, 13);
-  if (IRC_SCAN_SEL_STOP == 4 && mode == SEL_FINAL) return;
   const int cnt = (int)(M < (uint32_t)k ? M : (uint32_t)k);
   if (cnt <= SEL_NT) {
     // winner tid goes to its rank (keys are distinct); slots past cnt are empty
@@ -979,13 +936,8 @@ __device__ __forceinline__ void select_body(Src src, int k, int mode,
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
   const int lane = tid & 63;
-#define SEL_STOP(n)                                                     \
-  do {                                                                  \
-    if (IRC_SCAN_SEL_STOP == (n) && mode == SEL_FINAL) return;          \
-  } while (0)
 
   STAMP(mode, 0);
-  SEL_STOP(0);
   if (tid == 0) {
     s_misc[0] = 0;
     s_misc[3] = 0;
@@ -1043,7 +995,6 @@ __device__ __forceinline__ void select_body(Src src, int k, int mode,
   const bool staged = M <= (uint32_t)SEL_STAGE;
   __syncthreads();
   STAMP(mode, 1);
-  SEL_STOP(1);
   if constexpr (Src::kRegions) {
     if (table && staged) {
       select_fast<Src, BIGK>(src, q, k, mode, M, rid, roff,
@@ -1735,15 +1686,19 @@ __global__ __launch_bounds__(SEL_NT) void select_dense_kernel(DenseArgs a) {
 // One 256-thread workgroup per query (a wave-per-query variant made the whole call
 // 40 us slower at Q = 1 and 35 us at Q = 256 on MI355X, 100k x 768, k = 100: one wave
 // walked every region and every radix pass alone; removed in round 6).
-static void launch_select(const RegionSource& src, int Q, int k, int mode, uint64_t* thr,
+template <class Src>
+static void launch_select(const Src& src, int64_t Q, int64_t k, int mode, uint64_t* thr,
                           float* out_score, int64_t* out_idx, float smul, hipStream_t st) {
   if (k > 512)
-      hipLaunchKernelGGL((select_kernel_bigk<RegionSource>), dim3((unsigned)Q), dim3(SEL_NT), 0,
-                         st, src, k, mode, thr, out_score, out_idx, smul);
-    else
-      hipLaunchKernelGGL((select_kernel<RegionSource>), dim3((unsigned)Q), dim3(SEL_NT), 0, st,
-                         src, k, mode, thr, out_score, out_idx, smul);
+    hipLaunchKernelGGL((select_kernel_bigk<Src>), dim3((unsigned)Q), dim3(SEL_NT), 0, st, src,
+                       (int)k, mode, thr, out_score, out_idx, smul);
+  else
+    hipLaunchKernelGGL((select_kernel<Src>), dim3((unsigned)Q), dim3(SEL_NT), 0, st, src, (int)k,
+                       mode, thr, out_score, out_idx, smul);
 }
+// Kernels lie in the code object in their order of instantiation.  This line and its like
+// ahead of scan_topk_impl pin that order, so rearranging host code moves no device code.
+template decltype(launch_select<RegionSource>) launch_select<RegionSource>;
 
 // Threshold of the sampled pipeline from the GEMM kernel's sample lists (the 4
 // largest keys of every (256-doc sample tile, query)): thr[q] = the exact k-th largest
@@ -1771,31 +1726,48 @@ __global__ __launch_bounds__(SEL_NT) void lists_kth_kernel(const uint64_t* __res
 }
 
 // ------------------------------------------------------------------ planning
+// The passes of one scan, chosen by make_plan alone (irc_scan_topk_pipeline reports them).
+// The threshold pass over a strided sample of the shard:
+enum class Sample {
+  None = IRC_SCAN_SAMPLE_NONE,  // no threshold: the filter keeps every key, or keeps lists
+  Tile = IRC_SCAN_SAMPLE_TILE,  // scan_tile_kernel<GMAX>, then select_kernel(SEL_THRESHOLD)
+  Gemm = IRC_SCAN_SAMPLE_GEMM,  // run_scan with lists over the sample, then lists_kth_kernel
+};
+// The pass over every doc, and the select that belongs to it:
+enum class Filter {
+  // single pass on scan_tile_kernel<LTOP> (Q <= ltop_max_q): each lane's 4 largest keys,
+  // select_dense_kernel<KS>
+  TileLists = IRC_SCAN_FILTER_TILE_LISTS,
+  // single pass on the ping-pong GEMM (Q in [ppl_min_q, 256]): the 4 largest keys per
+  // (256-doc tile, query), select_dense_kernel<KS = 0>
+  GemmLists = IRC_SCAN_FILTER_GEMM_LISTS,
+  // run_scan with the threshold epilogue (Q >= pp_min_q): regions = 256-doc tiles,
+  // select_kernel(SEL_FINAL)
+  GemmKeys = IRC_SCAN_FILTER_GEMM_KEYS,
+  // scan_tile_kernel<KEYS>, select_kernel(SEL_FINAL)
+  TileKeys = IRC_SCAN_FILTER_TILE_KEYS,
+};
+
 struct Plan {
   int nw;  // waves = nq * ks
   int nq;  // 32-query groups per workgroup
   int ks;  // k-slices (D split across a wave pair)
   int qpad;
   int gy;
-  bool two_phase;
+  Sample sample;
+  Filter filter;
   int64_t stride;  // sample stride
   int64_t S;       // sample size
   int g_s, tpw_s;
   int64_t cap_s;
   int g_f, tpw_f;
   int64_t cap_f;
-  // single-pass LTOP scan + select_dense (no sample, no threshold select)
-  bool ltop;
-  int ls;  // lists per query
-  // filter pass on the ping-pong GEMM (Q >= pp_min_q): regions = 256-doc tiles
-  bool pp;
-  // single pass on the ping-pong GEMM (Q in [ppl_min_q, 256]): lists of the 4 largest
-  // keys per (256-doc tile, query), select_dense<KS = 0>; no sample, no threshold
-  bool ppl;
-  int pp_sG;  // 256-doc tiles of the threshold sample on the GEMM kernel (pp two-phase)
+  int ls;     // TileLists: lists per query
+  int pp_sG;  // Sample::Gemm: 256-doc tiles of the sample
   int pp_G, pp_qpad;
   int64_t pp_cap;
   size_t off_thr, off_cnt, off_keys, bytes;
+  bool gemm_filter() const { return filter == Filter::GemmLists || filter == Filter::GemmKeys; }
 };
 
 // IRC_SCAN_PP_MINQ sets the GEMM-kernel filter's Q floor (default 192; a value above
@@ -1868,20 +1840,33 @@ static size_t tile_lds_bytes() {
 // 33 / 64: 90.7 / 94.0 -> 90.2 / 95.6 us), so off there.
 constexpr int LTOP_KS4_GROUPS = 1;
 
-template <int EB>
-static size_t lds_bytes_eb(int64_t D) {
+template <int V>
+using ic = std::integral_constant<int, V>;
+
+// f(ic<D>{}) for a supported width (supported_d); false, and no call, for any other.
+template <class F>
+static bool with_d(int64_t D, F&& f) {
   switch (D) {
-    case 64: return tile_lds_bytes<64, EB>();
-    case 128: return tile_lds_bytes<128, EB>();
-    case 256: return tile_lds_bytes<256, EB>();
-    case 384: return tile_lds_bytes<384, EB>();
-    case 512: return tile_lds_bytes<512, EB>();
-    case 768: return tile_lds_bytes<768, EB>();
-    default: return tile_lds_bytes<1024, EB>();
+    case 64: f(ic<64>{}); return true;
+    case 128: f(ic<128>{}); return true;
+    case 256: f(ic<256>{}); return true;
+    case 384: f(ic<384>{}); return true;
+    case 512: f(ic<512>{}); return true;
+    case 768: f(ic<768>{}); return true;
+    case 1024: f(ic<1024>{}); return true;
+    default: return false;
   }
 }
+
 static size_t lds_bytes_for(int64_t D, int eb) {
-  return eb == 1 ? lds_bytes_eb<1>(D) : lds_bytes_eb<2>(D);
+  size_t bytes = 0;
+  auto f = [&](auto d) {
+    constexpr int DD = decltype(d)::value;
+    bytes = eb == 1 ? tile_lds_bytes<DD, 1>() : tile_lds_bytes<DD, 2>();
+  };
+  // the workspace queries size a plan before any check of D: the widest tile then
+  if (!with_d(D, f)) f(ic<1024>{});
+  return bytes;
 }
 
 // Workers own contiguous tile ranges; the worker count is a multiple of 8 so the
@@ -1930,49 +1915,63 @@ static Plan make_plan(int64_t Q, int64_t N, int64_t D, int64_t k, int eb) {
   if (s_target > s_cap) s_target = s_cap;
   p.stride = s_target > 0 ? N / s_target : 1;
   if (p.stride < 1) p.stride = 1;
-  p.two_phase = p.stride > 1;
-  p.S = p.two_phase ? (N + p.stride - 1) / p.stride : N;
+  const bool sampled = p.stride > 1;
+  p.S = sampled ? (N + p.stride - 1) / p.stride : N;
   plan_workers((p.S + TD - 1) / TD, p.gy, D, eb, p.nw, &p.g_s, &p.tpw_s);
   p.cap_s = (int64_t)p.tpw_s * TD;
   plan_workers((N + TD - 1) / TD, p.gy, D, eb, p.nw, &p.g_f, &p.tpw_f);
   p.cap_f = (int64_t)p.tpw_f * TD;
   const int gmax = p.g_s > p.g_f ? p.g_s : p.g_f;
   int64_t kmax = (int64_t)p.g_f * p.cap_f;
-  if (p.two_phase && (int64_t)p.g_s * p.cap_s > kmax) kmax = (int64_t)p.g_s * p.cap_s;
+  if (sampled && (int64_t)p.g_s * p.cap_s > kmax) kmax = (int64_t)p.g_s * p.cap_s;
   size_t cnt_bytes = (size_t)gmax * p.qpad * 2 * p.ks * 4;
   size_t key_bytes = (size_t)kmax * p.qpad * 8;
   p.pp_G = (int)((N + 255) / 256);
   p.pp_qpad = (int)((Q + 255) / 256 * 256);
   p.pp_cap = 256;  // a 256-doc tile can never overflow its region
-  const size_t pp_keys = (size_t)p.pp_G * p.pp_qpad * p.pp_cap * 8;
-  // the GEMM-kernel filter: bf16, or fp8 with 128-byte K-tiles (D % 128 == 0)
-  p.pp = (eb == 2 || D % 128 == 0) && Q >= pp_min_q() && N >= 256 &&
-         pp_keys <= pp_max_bytes() && p.pp_G <= SEL_MAXR;
   p.pp_sG = (int)((p.S + 255) / 256);
-  if (p.pp && p.two_phase) {  // the GEMM sample's lists share the survivor key buffer
-    const size_t sb = (size_t)Q * p.pp_sG * LT_M * 8;
-    if (sb > key_bytes) key_bytes = sb;
-  }
-  if (p.pp) {
+  p.ls = p.g_f * 2 * p.ks;
+  const size_t pp_keys = (size_t)p.pp_G * p.pp_qpad * p.pp_cap * 8;
+  // the GEMM kernel: bf16, or fp8 with 128-byte K-tiles (D % 128 == 0)
+  const bool gemm_ok = (eb == 2 || D % 128 == 0) && N >= 256;
+  const bool gemm_keys =
+      gemm_ok && Q >= pp_min_q() && pp_keys <= pp_max_bytes() && p.pp_G <= SEL_MAXR;
+  // the single-pass GEMM filter: one query tile, every tile's list in one select stage
+  const bool gemm_lists = gemm_ok && Q >= ppl_min_q() && Q <= 256 &&
+                          (int64_t)p.pp_G * LT_M <= SEL_STAGE && k <= SEL_NT;
+  // LTOP where the GEMM filter does not run and all lists fit one select stage
+  const bool tile_lists = Q <= ltop_max_q() && (int64_t)p.ls * LT_M <= SEL_STAGE && k <= SEL_NT;
+  p.filter = gemm_lists ? Filter::GemmLists
+             : gemm_keys ? Filter::GemmKeys
+             : tile_lists ? Filter::TileLists
+                          : Filter::TileKeys;
+  // The threshold sample runs on the GEMM kernel (the sample docs, every stride-th row, as B
+  // with row stride ldb = stride * D) only where its lists hold >= 4 k keys: C2's 6,250-doc
+  // sample has 25 tiles = 100 keys, no threshold at k = 100, every doc survives -- 640 us a
+  // call, profiles/r04_b_ppl_ab.txt; the tile kernel's GMAX pass keeps 4 keys per 32 docs.
+  // (That pass ran at ~0.05 of the MFMA peak at Q = 2048: 699 us of a 3.3 ms C4 call,
+  // profiles/r03_scan_p_kernels.txt.)
+  const int64_t sample_keys = (int64_t)p.pp_sG * LT_M;
+  if (!sampled || p.filter == Filter::GemmLists || p.filter == Filter::TileLists)
+    p.sample = Sample::None;
+  else if (p.filter == Filter::GemmKeys && sample_keys <= SEL_STAGE && sample_keys >= 4 * k)
+    p.sample = Sample::Gemm;
+  else
+    p.sample = Sample::Tile;
+  // every buffer any pass of the plan may use (the GEMM sample's lists share the survivor
+  // key buffer)
+  if (gemm_keys) {
+    const size_t sb = sampled ? (size_t)Q * p.pp_sG * LT_M * 8 : 0;
     const size_t pc = (size_t)p.pp_G * p.pp_qpad * 4;
+    if (sb > key_bytes) key_bytes = sb;
     if (pc > cnt_bytes) cnt_bytes = pc;
     if (pp_keys > key_bytes) key_bytes = pp_keys;
   }
-  // the single-pass GEMM filter: one query tile, every tile's list in one select stage
-  p.ppl = Q >= ppl_min_q() && Q <= 256 && N >= 256 && (eb == 2 || D % 128 == 0) &&
-          (int64_t)p.pp_G * LT_M <= SEL_STAGE && k <= SEL_NT;
-  if (p.ppl) {
-    p.pp = false;
-    p.two_phase = false;
+  if (gemm_lists) {
     const size_t lb = (size_t)Q * p.pp_G * LT_M * 8;
     if (lb > key_bytes) key_bytes = lb;
   }
-  // LTOP where the GEMM filter does not run and all lists fit one select stage
-  p.ls = p.g_f * 2 * p.ks;
-  p.ltop = !p.pp && !p.ppl && Q <= ltop_max_q() && (int64_t)p.ls * LT_M <= SEL_STAGE &&
-           k <= SEL_NT;
-  if (p.ltop) {
-    p.two_phase = false;
+  if (p.filter == Filter::TileLists) {
     // four k-slices: same LDS (ring + a 16 KB exchange) and the same 4 lists per
     // worker and query (the half-lane lists are merged), so g_f / ls stand
     if (eb == 2 && (D == 768 || D == 1024) && p.nq <= LTOP_KS4_GROUPS) {
@@ -1983,7 +1982,7 @@ static Plan make_plan(int64_t Q, int64_t N, int64_t D, int64_t k, int eb) {
     if (lb > key_bytes) key_bytes = lb;
   }
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const int qthr = p.pp && p.pp_qpad > p.qpad ? p.pp_qpad : p.qpad;
+  const int qthr = p.filter == Filter::GemmKeys && p.pp_qpad > p.qpad ? p.pp_qpad : p.qpad;
   p.off_thr = 0;
   p.off_cnt = al(p.off_thr + (size_t)qthr * 8);
   p.off_keys = al(p.off_cnt + cnt_bytes);
@@ -2008,38 +2007,32 @@ static int dispatch_tile_eb(int64_t D, const Plan& p, int g, const unsigned char
                             const unsigned char* docs, int Q, int64_t NS, int64_t stride, int tpw,
                             uint32_t idx_base, const uint64_t* thr, uint64_t* keys,
                             uint32_t* counts, int64_t cap, float* scores, hipStream_t st) {
-#define IRC_SCAN_ARGS p, g, qs, docs, Q, NS, stride, tpw, idx_base, thr, keys, counts, cap, scores, st
-#define IRC_SCAN_CASE(DD)                                              \
-  case DD:                                                             \
-    if (p.ks == 4) {                                                   \
-      if constexpr ((MODE == LTOP || MODE == SCORES) && EB == 2 &&     \
-                    (DD == 768 || DD == 1024)) {                       \
-        if (p.nq == 1) launch_tile<DD, 1, MODE, EB, 4>(IRC_SCAN_ARGS); \
-        else launch_tile<DD, 2, MODE, EB, 4>(IRC_SCAN_ARGS);           \
-      } else {                                                         \
-        set_error("scan: four k-slices planned for an unsupported mode"); \
-        return IRC_E_INVALID;                                          \
-      }                                                                \
-    } else if (p.nq == 1) launch_tile<DD, 1, MODE, EB>(IRC_SCAN_ARGS); \
-    else if (p.nq == 2) launch_tile<DD, 2, MODE, EB>(IRC_SCAN_ARGS);   \
-    else if (p.nq == 4) launch_tile<DD, 4, MODE, EB>(IRC_SCAN_ARGS);   \
-    else launch_tile<DD, (DD > 512 ? 4 : 8), MODE, EB>(IRC_SCAN_ARGS); \
-    break;
-  switch (D) {
-    IRC_SCAN_CASE(64)
-    IRC_SCAN_CASE(128)
-    IRC_SCAN_CASE(256)
-    IRC_SCAN_CASE(384)
-    IRC_SCAN_CASE(512)
-    IRC_SCAN_CASE(768)
-    IRC_SCAN_CASE(1024)
-    default:
-      set_error("scan: unsupported D=%lld (supported: 64,128,256,384,512,768,1024)",
-                (long long)D);
-      return IRC_E_INVALID;
+  int rc = IRC_OK;
+  const bool known = with_d(D, [&](auto d) {
+    constexpr int DD = decltype(d)::value;
+    constexpr int KS = DD > 512 ? 2 : 1;
+    auto launch = [&](auto nq, auto ks) {
+      launch_tile<DD, decltype(nq)::value, MODE, EB, decltype(ks)::value>(
+          p, g, qs, docs, Q, NS, stride, tpw, idx_base, thr, keys, counts, cap, scores, st);
+    };
+    if (p.ks == 4) {
+      if constexpr ((MODE == LTOP || MODE == SCORES) && EB == 2 && (DD == 768 || DD == 1024)) {
+        if (p.nq == 1) launch(ic<1>{}, ic<4>{});
+        else launch(ic<2>{}, ic<4>{});
+      } else {
+        set_error("scan: four k-slices planned for an unsupported mode");
+        rc = IRC_E_INVALID;
+      }
+    } else if (p.nq == 1) launch(ic<1>{}, ic<KS>{});
+    else if (p.nq == 2) launch(ic<2>{}, ic<KS>{});
+    else if (p.nq == 4) launch(ic<4>{}, ic<KS>{});
+    else launch(ic<(DD > 512 ? 4 : 8)>{}, ic<KS>{});
+  });
+  if (!known) {
+    set_error("scan: unsupported D=%lld (supported: 64,128,256,384,512,768,1024)", (long long)D);
+    return IRC_E_INVALID;
   }
-#undef IRC_SCAN_CASE
-#undef IRC_SCAN_ARGS
+  if (rc) return rc;
   return check_launch("scan_tile_kernel");
 }
 
@@ -2059,40 +2052,29 @@ static int dispatch_tile(int eb, int64_t D, const Plan& p, int g, const void* qs
 
 template <int EB>
 static void launch_dense_eb(int64_t D, int ks, int Q, const DenseArgs& a, hipStream_t st) {
-#define IRC_DENSE_CASE(DD)                                                                 \
-  case DD:                                                                                 \
-    if (ks == 0) {                                                                         \
-      if constexpr (EB == 2 || DD % 128 == 0)                                              \
-        hipLaunchKernelGGL((select_dense_kernel<DD, EB, 0>), dim3((unsigned)Q), dim3(SEL_NT), 0, st, a); \
-      break;                                                                               \
-    }                                                                                      \
-    if constexpr (EB == 2 && (DD == 768 || DD == 1024)) {                                  \
-      if (ks == 4) {                                                                       \
-        hipLaunchKernelGGL((select_dense_kernel<DD, EB, 4>), dim3((unsigned)Q), dim3(SEL_NT), 0, st, a); \
-        break;                                                                             \
-      }                                                                                    \
-    }                                                                                      \
-    hipLaunchKernelGGL((select_dense_kernel<DD, EB, (DD > 512 ? 2 : 1)>), dim3((unsigned)Q), \
-                       dim3(SEL_NT), 0, st, a);                                            \
-    break;
-  switch (D) {
-    IRC_DENSE_CASE(64)
-    IRC_DENSE_CASE(128)
-    IRC_DENSE_CASE(256)
-    IRC_DENSE_CASE(384)
-    IRC_DENSE_CASE(512)
-    IRC_DENSE_CASE(768)
-    default: IRC_DENSE_CASE(1024)
-  }
-#undef IRC_DENSE_CASE
+  with_d(D, [&](auto d) {
+    constexpr int DD = decltype(d)::value;
+    if (ks == 0) {
+      if constexpr (EB == 2 || DD % 128 == 0)
+        hipLaunchKernelGGL((select_dense_kernel<DD, EB, 0>), dim3((unsigned)Q), dim3(SEL_NT), 0,
+                           st, a);
+      return;
+    }
+    if constexpr (EB == 2 && (DD == 768 || DD == 1024)) {
+      if (ks == 4) {
+        hipLaunchKernelGGL((select_dense_kernel<DD, EB, 4>), dim3((unsigned)Q), dim3(SEL_NT), 0,
+                           st, a);
+        return;
+      }
+    }
+    hipLaunchKernelGGL((select_dense_kernel<DD, EB, (DD > 512 ? 2 : 1)>), dim3((unsigned)Q),
+                       dim3(SEL_NT), 0, st, a);
+  });
 }
 static void launch_dense(int eb, int64_t D, int ks, int Q, const DenseArgs& a, hipStream_t st) {
   if (eb == 1) launch_dense_eb<1>(D, ks, Q, a, st);
   else launch_dense_eb<2>(D, ks, Q, a, st);
 }
-
-static void launch_select(const RegionSource& src, int Q, int k, int mode, uint64_t* thr,
-                          float* out_score, int64_t* out_idx, float smul, hipStream_t st);
 
 // Shards too large for the GEMM filter's plan (its survivor workspace, 2 KB per (256-doc
 // tile, query), over pp_max_bytes, or more tiles than the select's region table) are
@@ -2127,6 +2109,8 @@ static int scan_topk_impl(int eb, float smul, const void* queries, const void* d
                           int64_t workspace_bytes, float* out_score, int64_t* out_idx,
                           hipStream_t st);
 
+template decltype(launch_select<ListSource>) launch_select<ListSource>;  // kernel order, as above
+
 static int scan_topk_chunked(int eb, float smul, const void* queries, const void* docs, int64_t Q,
                              int64_t N, int64_t D, int64_t k, int64_t doc_offset, int64_t nc,
                              void* workspace, int64_t workspace_bytes, float* out_score,
@@ -2147,15 +2131,23 @@ static int scan_topk_chunked(int eb, float smul, const void* queries, const void
                                   st);
     if (rc) return rc;
   }
-  ListSource src{cs, ci, (int)nch, (int)Q, (int)k};
-  if (k > 512)
-    hipLaunchKernelGGL((select_kernel_bigk<ListSource>), dim3(Q), dim3(SEL_NT), 0, st, src, (int)k,
-                       (int)SEL_FINAL, nullptr, out_score, out_idx, 1.0f);
-  else
-    hipLaunchKernelGGL((select_kernel<ListSource>), dim3(Q), dim3(SEL_NT), 0, st, src, (int)k,
-                       (int)SEL_FINAL, nullptr, out_score, out_idx, 1.0f);
+  const ListSource src{cs, ci, (int)nch, (int)Q, (int)k};
+  launch_select(src, Q, k, SEL_FINAL, nullptr, out_score, out_idx, 1.0f, st);
   return check_launch("select_kernel(chunk merge)");
 }
+
+// The size checks of the scan, shared with irc_scan_topk_pipeline.
+static int check_sizes(int64_t Q, int64_t N, int64_t D, int64_t k) {
+  IRC_REQUIRE(Q >= 0 && N >= 0, "scan_topk: negative size");
+  IRC_REQUIRE(k >= 1 && k <= SEL_MAXK, "scan_topk: k=%lld outside [1, %d]", (long long)k,
+              SEL_MAXK);
+  IRC_REQUIRE(supported_d(D), "scan_topk: unsupported D=%lld", (long long)D);
+  IRC_REQUIRE(Q < (1 << 24), "scan_topk: Q too large");
+  IRC_REQUIRE(N < (1ll << 31) - 64, "scan_topk: shard too large (N < 2^31)");
+  return IRC_OK;
+}
+
+template decltype(dispatch_tile<LTOP>) dispatch_tile<LTOP>;  // kernel order: see launch_select
 
 // The scan for both element widths (eb = 2: bf16, 1: e4m3; smul scales the
 // returned scores, 1 for bf16).
@@ -2163,14 +2155,10 @@ static int scan_topk_impl(int eb, float smul, const void* queries, const void* d
                           int64_t N, int64_t D, int64_t k, int64_t doc_offset, void* workspace,
                           int64_t workspace_bytes, float* out_score, int64_t* out_idx,
                           hipStream_t st) {
-  IRC_REQUIRE(Q >= 0 && N >= 0, "scan_topk: negative size");
-  IRC_REQUIRE(k >= 1 && k <= SEL_MAXK, "scan_topk: k=%lld outside [1, %d]", (long long)k,
-              SEL_MAXK);
-  IRC_REQUIRE(supported_d(D), "scan_topk: unsupported D=%lld", (long long)D);
+  int rc;
+  if ((rc = check_sizes(Q, N, D, k))) return rc;
   IRC_REQUIRE(doc_offset >= 0 && doc_offset + N <= (int64_t)0xFFFFFFFFll,
               "scan_topk: global doc index must fit 32 bits");
-  IRC_REQUIRE(Q < (1 << 24), "scan_topk: Q too large");
-  IRC_REQUIRE(N < (1ll << 31) - 64, "scan_topk: shard too large (N < 2^31)");
   IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
               "scan_topk: queries and docs must be 16-byte aligned");
   if (Q == 0) return IRC_OK;
@@ -2193,122 +2181,104 @@ static int scan_topk_impl(int eb, float smul, const void* queries, const void* d
   uint64_t* thr = reinterpret_cast<uint64_t*>(ws + p.off_thr);
   uint32_t* cnt = reinterpret_cast<uint32_t*>(ws + p.off_cnt);
   uint64_t* keys = reinterpret_cast<uint64_t*>(ws + p.off_keys);
+  const unsigned char* q8 = static_cast<const unsigned char*>(queries);
+  const unsigned char* d8 = static_cast<const unsigned char*>(docs);
   const uint32_t base = (uint32_t)doc_offset;
   const double alg_bytes = (double)N * D * eb + (double)Q * D * eb;
-  int rc;
-  if (p.ltop) {
-    prof_begin(st);
-    rc = dispatch_tile<LTOP>(eb, D, p, p.g_f, queries, docs, (int)Q, N, 1, p.tpw_f, base, nullptr,
-                             keys, cnt, p.ls, nullptr, st);
-    prof_end("scan_filter", st, alg_bytes);
-    if (rc) return rc;
-    DenseArgs da{keys, static_cast<const unsigned char*>(queries),
-                 static_cast<const unsigned char*>(docs), p.ls, (int)N, p.tpw_f, base, (int)k, smul,
-                 out_score, out_idx};
-    launch_dense(eb, D, p.ks, (int)Q, da, st);
-    return check_launch("select_dense_kernel");
+
+  switch (p.sample) {  // thr[q]: a lower bound of the query's k-th key
+    case Sample::None:
+      thr = nullptr;
+      break;
+    case Sample::Tile: {
+      rc = dispatch_tile<GMAX>(eb, D, p, p.g_s, queries, docs, (int)Q, p.S, p.stride, p.tpw_s,
+                               base, nullptr, keys, cnt, p.cap_s, nullptr, st);
+      if (rc) return rc;
+      const RegionSource s1 = region_source(keys, cnt, p.g_s, p.qpad, p.cap_s, 2 * p.ks);
+      launch_select(s1, Q, k, SEL_THRESHOLD, thr, nullptr, nullptr, 1.0f, st);
+      if ((rc = check_launch("select_kernel(threshold)"))) return rc;
+      break;
+    }
+    case Sample::Gemm: {
+      // the 4 largest keys per (256-doc sample tile, query), thr[q] = their k-th
+      gpp::PArgs a = gpp::qd_pass(queries, docs, Q, p.S, D, eb == 1);
+      a.ldb *= p.stride;  // every stride-th row
+      a.alpha = 1.f;
+      a.qpad = p.pp_qpad;
+      a.stride = (int)p.stride;
+      a.idx_base = base;
+      a.lists = keys;
+      a.ls = p.pp_sG;
+      gpp::run_scan(a, st, eb == 1);
+      if ((rc = check_launch("gemm_pp_kernel(scan sample)"))) return rc;
+      hipLaunchKernelGGL(lists_kth_kernel, dim3((unsigned)Q), dim3(SEL_NT), 0, st, keys, p.pp_sG,
+                         (int)k, thr);
+      if ((rc = check_launch("lists_kth_kernel"))) return rc;
+      break;
+    }
   }
-  if (p.ppl) {
-    // single pass: the GEMM filter keeps the 4 largest keys of every (256-doc tile,
-    // query); select_dense takes the k-th of all lists and rescans the tiles whose
-    // 4th key reaches it
-    gpp::PArgs a{};
-    a.A = static_cast<const unsigned short*>(queries);
-    a.B = static_cast<const unsigned short*>(docs);
-    a.M = (int)Q;
-    a.N = (int)N;
-    a.K = (int)(D * eb / 2);  // 2-byte units
-    a.kchunk = a.K;
-    a.lda = a.K;
-    a.ldb = a.K;
-    a.alpha = 1.f;
-    a.qpad = p.pp_qpad;
-    a.stride = 1;
-    a.idx_base = base;
-    a.lists = keys;
-    a.ls = p.pp_G;
-    prof_begin(st);
-    gpp::run_scan(a, st, eb == 1);
-    prof_end("scan_filter", st, alg_bytes);
-    if ((rc = check_launch("gemm_pp_kernel(scan lists)"))) return rc;
-    DenseArgs da{keys, static_cast<const unsigned char*>(queries),
-                 static_cast<const unsigned char*>(docs), p.pp_G, (int)N, 256 / TD, base, (int)k,
-                 smul, out_score, out_idx};
-    launch_dense(eb, D, 0, (int)Q, da, st);
-    return check_launch("select_dense_kernel(gemm lists)");
-  }
-  if (p.two_phase && p.pp && p.pp_sG * LT_M <= SEL_STAGE &&
-      p.pp_sG * LT_M >= 4 * k) {
-    // threshold sample on the GEMM kernel: the sample docs (every stride-th row) as B
-    // with row stride ldb = stride * D, the 4 largest keys per (256-doc sample tile,
-    // query) kept, thr[q] = their k-th.  Only where the lists hold >= 4 k keys (C2's
-    // 6,250-doc sample has 25 tiles = 100 keys: no threshold at k = 100, every doc
-    // survives -- 640 us a call, profiles/r04_b_ppl_ab.txt; the tile kernel's GMAX
-    // pass keeps 4 keys per 32 docs).  (The tile kernel's GMAX pass ran at ~0.05 of
-    // the MFMA peak at Q = 2048: 699 us of a 3.3 ms C4 call, profiles/r03_scan_p_kernels.txt.)
-    gpp::PArgs a{};
-    a.A = static_cast<const unsigned short*>(queries);
-    a.B = static_cast<const unsigned short*>(docs);
-    a.M = (int)Q;
-    a.N = (int)p.S;
-    a.K = (int)(D * eb / 2);  // 2-byte units
-    a.kchunk = a.K;
-    a.lda = a.K;
-    a.ldb = (int64_t)a.K * p.stride;
-    a.alpha = 1.f;
-    a.qpad = p.pp_qpad;
-    a.stride = (int)p.stride;
-    a.idx_base = base;
-    a.lists = keys;
-    a.ls = p.pp_sG;
-    gpp::run_scan(a, st, eb == 1);
-    if ((rc = check_launch("gemm_pp_kernel(scan sample)"))) return rc;
-    hipLaunchKernelGGL(lists_kth_kernel, dim3((unsigned)Q), dim3(SEL_NT), 0, st, keys, p.pp_sG,
-                       (int)k, thr);
-    if ((rc = check_launch("lists_kth_kernel"))) return rc;
-  } else if (p.two_phase) {
-    rc = dispatch_tile<GMAX>(eb, D, p, p.g_s, queries, docs, (int)Q, p.S, p.stride, p.tpw_s,
-                             base, nullptr, keys, cnt, p.cap_s, nullptr, st);
-    if (rc) return rc;
-    const RegionSource s1 = region_source(keys, cnt, p.g_s, p.qpad, p.cap_s, 2 * p.ks);
-    launch_select(s1, (int)Q, (int)k, SEL_THRESHOLD, thr, nullptr, nullptr, 1.0f, st);
-    if ((rc = check_launch("select_kernel(threshold)"))) return rc;
-  }
-  if (p.pp) {
-    // filter = NT GEMM C[q][doc] = Q . Docs^T on the ping-pong kernel with a
-    // threshold epilogue; regions are (256-doc tile, query) with cap 256.
-    gpp::PArgs a{};
-    a.A = static_cast<const unsigned short*>(queries);
-    a.B = static_cast<const unsigned short*>(docs);
-    a.M = (int)Q;
-    a.N = (int)N;
-    a.K = (int)(D * eb / 2);  // 2-byte units
-    a.kchunk = a.K;
-    a.lda = a.K;
-    a.ldb = a.K;
-    a.alpha = 1.f;
-    a.thr = p.two_phase ? thr : nullptr;
-    a.keys = keys;
-    a.counts = cnt;
-    a.cap = p.pp_cap;
-    a.qpad = p.pp_qpad;
-    a.stride = 1;
-    a.idx_base = base;
-    prof_begin(st);
-    gpp::run_scan(a, st, eb == 1);
-    prof_end("scan_filter", st, alg_bytes);
-    if ((rc = check_launch("gemm_pp_kernel(scan)"))) return rc;
-    const RegionSource s2 = region_source(keys, cnt, p.pp_G, p.pp_qpad, p.pp_cap, 1);
-    launch_select(s2, (int)Q, (int)k, SEL_FINAL, nullptr, out_score, out_idx, smul, st);
-    return check_launch("select_kernel(final)");
+
+  switch (p.filter) {
+    case Filter::TileLists: {
+      prof_begin(st);
+      rc = dispatch_tile<LTOP>(eb, D, p, p.g_f, queries, docs, (int)Q, N, 1, p.tpw_f, base,
+                               nullptr, keys, cnt, p.ls, nullptr, st);
+      prof_end("scan_filter", st, alg_bytes);
+      if (rc) return rc;
+      const DenseArgs da{keys, q8, d8, p.ls, (int)N, p.tpw_f, base, (int)k, smul, out_score,
+                         out_idx};
+      launch_dense(eb, D, p.ks, (int)Q, da, st);
+      return check_launch("select_dense_kernel");
+    }
+    case Filter::GemmLists: {
+      // select_dense takes the k-th of all lists and rescans the tiles whose 4th key
+      // reaches it
+      gpp::PArgs a = gpp::qd_pass(queries, docs, Q, N, D, eb == 1);
+      a.alpha = 1.f;
+      a.qpad = p.pp_qpad;
+      a.stride = 1;
+      a.idx_base = base;
+      a.lists = keys;
+      a.ls = p.pp_G;
+      prof_begin(st);
+      gpp::run_scan(a, st, eb == 1);
+      prof_end("scan_filter", st, alg_bytes);
+      if ((rc = check_launch("gemm_pp_kernel(scan lists)"))) return rc;
+      const DenseArgs da{keys, q8, d8, p.pp_G, (int)N, 256 / TD, base, (int)k, smul, out_score,
+                         out_idx};
+      launch_dense(eb, D, 0, (int)Q, da, st);
+      return check_launch("select_dense_kernel(gemm lists)");
+    }
+    case Filter::GemmKeys: {
+      // the NT GEMM C[q][doc] = Q . Docs^T with a threshold epilogue; regions are
+      // (256-doc tile, query) with cap 256
+      gpp::PArgs a = gpp::qd_pass(queries, docs, Q, N, D, eb == 1);
+      a.alpha = 1.f;
+      a.thr = thr;
+      a.keys = keys;
+      a.counts = cnt;
+      a.cap = p.pp_cap;
+      a.qpad = p.pp_qpad;
+      a.stride = 1;
+      a.idx_base = base;
+      prof_begin(st);
+      gpp::run_scan(a, st, eb == 1);
+      prof_end("scan_filter", st, alg_bytes);
+      if ((rc = check_launch("gemm_pp_kernel(scan)"))) return rc;
+      const RegionSource s2 = region_source(keys, cnt, p.pp_G, p.pp_qpad, p.pp_cap, 1);
+      launch_select(s2, Q, k, SEL_FINAL, nullptr, out_score, out_idx, smul, st);
+      return check_launch("select_kernel(final)");
+    }
+    case Filter::TileKeys:  // below
+      break;
   }
   prof_begin(st);
-  rc = dispatch_tile<KEYS>(eb, D, p, p.g_f, queries, docs, (int)Q, N, 1, p.tpw_f, base,
-                           p.two_phase ? thr : nullptr, keys, cnt, p.cap_f, nullptr, st);
+  rc = dispatch_tile<KEYS>(eb, D, p, p.g_f, queries, docs, (int)Q, N, 1, p.tpw_f, base, thr, keys,
+                           cnt, p.cap_f, nullptr, st);
   prof_end("scan_filter", st, alg_bytes);  // algorithmic bytes
   if (rc) return rc;
   const RegionSource s2 = region_source(keys, cnt, p.g_f, p.qpad, p.cap_f, 2 * p.ks);
-  launch_select(s2, (int)Q, (int)k, SEL_FINAL, nullptr, out_score, out_idx, smul, st);
+  launch_select(s2, Q, k, SEL_FINAL, nullptr, out_score, out_idx, smul, st);
   return check_launch("select_kernel(final)");
 }
 
@@ -2361,6 +2331,21 @@ extern "C" int irc_scan_rescan_stats(uint64_t* out, int reset) {
 // Smallest query batch of the single-pass GEMM filter (Q in [q, 256]); > 256 turns it
 // off (the sampled-threshold pipeline then runs).  Returns the previous value.
 extern "C" int irc_scan_set_ppl_min_q(int q) { return ppl_min_q_ref().exchange(q); }
+
+// The passes irc_scan_topk (fp8: irc_scan_topk_fp8) runs for a shape under the current knobs:
+// host arithmetic only.
+extern "C" int irc_scan_topk_pipeline(int64_t Q, int64_t N, int64_t D, int64_t k, int fp8,
+                                      int* sample, int* filter, int64_t* chunk_docs_out) {
+  IRC_REQUIRE(sample && filter && chunk_docs_out, "scan_topk_pipeline: null pointer");
+  if (int rc = check_sizes(Q, N, D, k)) return rc;
+  const int eb = fp8 ? 1 : 2;
+  const int64_t nc = std::min(chunk_docs(Q, N, D, k, eb), N);
+  const Plan p = make_plan(Q, nc, D, k, eb);
+  *sample = (int)p.sample;
+  *filter = (int)p.filter;
+  *chunk_docs_out = nc;
+  return IRC_OK;
+}
 
 extern "C" int64_t irc_scan_topk_workspace(int64_t Q, int64_t N, int64_t D, int64_t k) {
   if (Q <= 0 || N <= 0 || k <= 0) return 256;
@@ -2491,14 +2476,8 @@ extern "C" int irc_topk_merge(const float* in_score, const int64_t* in_idx, int6
   IRC_REQUIRE(P >= 1 && Q >= 0 && kin >= 1, "topk_merge: bad sizes");
   IRC_REQUIRE(kout >= 1 && kout <= SEL_MAXK, "topk_merge: kout outside [1, %d]", SEL_MAXK);
   if (Q == 0) return IRC_OK;
-  ListSource src{in_score, in_idx, (int)P, (int)Q, (int)kin};
-  if (kout > 512)
-    hipLaunchKernelGGL((select_kernel_bigk<ListSource>), dim3(Q), dim3(SEL_NT), 0,
-                       as_stream(stream), src, (int)kout, (int)SEL_FINAL, nullptr, out_score,
-                       out_idx, 1.0f);
-  else
-    hipLaunchKernelGGL((select_kernel<ListSource>), dim3(Q), dim3(SEL_NT), 0, as_stream(stream),
-                       src, (int)kout, (int)SEL_FINAL, nullptr, out_score, out_idx, 1.0f);
+  const ListSource src{in_score, in_idx, (int)P, (int)Q, (int)kin};
+  launch_select(src, Q, kout, SEL_FINAL, nullptr, out_score, out_idx, 1.0f, as_stream(stream));
   return check_launch("select_kernel(merge)");
 }
 
@@ -2509,19 +2488,11 @@ extern "C" int irc_scan_scores(const void* queries, const void* docs, int64_t Q,
   IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
               "scan_scores: queries and docs must be 16-byte aligned");
   if (Q == 0 || N == 0) return IRC_OK;
-  Plan p = make_plan(Q, N, D, 1, 2);
-  if (p.pp || p.ppl) {
+  const Plan p = make_plan(Q, N, D, 1, 2);
+  if (p.gemm_filter()) {
     // same MFMA arithmetic as irc_scan_topk's filter on this path
-    gpp::PArgs a{};
-    a.A = static_cast<const unsigned short*>(queries);
-    a.B = static_cast<const unsigned short*>(docs);
+    gpp::PArgs a = gpp::qd_pass(queries, docs, Q, N, D, false);
     a.C = out;
-    a.M = (int)Q;
-    a.N = (int)N;
-    a.K = (int)D;
-    a.kchunk = (int)D;
-    a.lda = D;
-    a.ldb = D;
     a.ldc = N;
     a.alpha = 1.f;
     a.vec_c = (N % 8 == 0) && ((uintptr_t)out % 16) == 0;
@@ -2541,19 +2512,11 @@ extern "C" int irc_scan_scores_fp8(const void* queries, const void* docs, int64_
   IRC_REQUIRE(((uintptr_t)queries % 16) == 0 && ((uintptr_t)docs % 16) == 0,
               "scan_scores_fp8: queries and docs must be 16-byte aligned");
   if (Q == 0 || N == 0) return IRC_OK;
-  Plan p = make_plan(Q, N, D, 1, 1);
-  if (p.pp || p.ppl) {
+  const Plan p = make_plan(Q, N, D, 1, 1);
+  if (p.gemm_filter()) {
     // same MFMA arithmetic as irc_scan_topk_fp8's filter on this path
-    gpp::PArgs a{};
-    a.A = static_cast<const unsigned short*>(queries);
-    a.B = static_cast<const unsigned short*>(docs);
+    gpp::PArgs a = gpp::qd_pass(queries, docs, Q, N, D, true);
     a.C = out;
-    a.M = (int)Q;
-    a.N = (int)N;
-    a.K = (int)(D / 2);
-    a.kchunk = a.K;
-    a.lda = a.K;
-    a.ldb = a.K;
     a.ldc = N;
     a.alpha = 1.f;
     a.vec_c = (N % 8 == 0) && ((uintptr_t)out % 16) == 0;

@@ -99,6 +99,7 @@ SIGNATURES = {
     "irc_gemm_l2_touch_map": (I64, [I32, I64, I64, I64, I64, I64, I64, P, P, P]),
     "irc_gemm_set_pp": (I32, [I32]),
     "irc_scan_set_ppl_min_q": (I32, [I32]),
+    "irc_scan_topk_pipeline": (I32, [I64, I64, I64, I64, I32, P, P, P]),
     "irc_embed_ln": (I32, [I32, P, P, P, P, P, P, P, I64, I64, I64, F32, P]),
     "irc_layernorm": (I32, [I32, P, P, P, P, I64, I64, F32, P]),
     "irc_attention": (I32, [I32, P, P, P, I64, I64, I64, I64, P]),

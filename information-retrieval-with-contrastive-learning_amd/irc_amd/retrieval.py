@@ -163,6 +163,25 @@ def set_single_pass_min_q(q: int) -> int:
     return int(_lib.load().irc_scan_set_ppl_min_q(int(q)))
 
 
+SCAN_SAMPLES = ("none", "tile", "gemm")  # irc.h: IRC_SCAN_SAMPLE_*
+SCAN_FILTERS = ("tile_lists", "gemm_lists", "gemm_keys", "tile_keys")  # IRC_SCAN_FILTER_*
+
+
+def scan_pipeline(Q: int, N: int, D: int, k: int, dtype: str = "bf16"):
+    """(sample, filter, chunk_docs): the passes ``scan_topk`` (dtype "e4m3": ``scan_topk_fp8``)
+    runs for the shape under the current knobs, by name (irc_scan_topk_pipeline; tests /
+    diagnostics).  chunk_docs = N, or the chunk size where the shard is scanned in chunks;
+    the pair describes one chunk.  Host arithmetic only: no device is accessed."""
+    import ctypes
+
+    if dtype not in ("bf16", "e4m3"):
+        raise ValueError(f"scan_pipeline: dtype {dtype!r} is neither 'bf16' nor 'e4m3'")
+    s, f, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    _lib.call("irc_scan_topk_pipeline", Q, N, D, k, int(dtype == "e4m3"), ctypes.addressof(s),
+              ctypes.addressof(f), ctypes.addressof(c))
+    return SCAN_SAMPLES[s.value], SCAN_FILTERS[f.value], int(c.value)
+
+
 def rescan_stats(reset: bool = True):
     """(queries whose single-pass select rescanned, workers rescanned) since the
     last reset -- synchronises the device (tests / diagnostics)."""

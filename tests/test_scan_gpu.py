@@ -126,6 +126,46 @@ def test_topk_exact_vs_oracle_single_pass(gpu, Q, N, D, k, off):
     np.testing.assert_array_equal(s.cpu().numpy(), rs)
 
 
+# one small shape per reachable (sample, filter) pair of the plan (scan_topk.hip make_plan);
+# the three pairs on the GEMM kernel also as e4m3
+PIPELINES = [
+    ("none", "tile_lists", 33, 4099, 768, 10, "bf16"),  # four k-slices, two groups
+    ("none", "tile_keys", 65, 300, 64, 10, "bf16"),
+    ("tile", "tile_keys", 65, 20000, 128, 4, "bf16"),
+    ("none", "gemm_keys", 192, 300, 128, 10, "bf16"),
+    ("tile", "gemm_keys", 192, 20000, 128, 100, "bf16"),
+    ("gemm", "gemm_keys", 192, 20000, 128, 4, "bf16"),  # 5 sample tiles: 20 list keys >= 16
+    ("none", "gemm_lists", 100, 4099, 128, 10, "bf16"),  # under _single_pass()
+    ("none", "gemm_keys", 192, 300, 128, 10, "e4m3"),
+    ("tile", "gemm_keys", 192, 20000, 128, 100, "e4m3"),
+    ("gemm", "gemm_keys", 192, 20000, 128, 4, "e4m3"),
+]
+
+
+@pytest.mark.parametrize("sample,filt,Q,N,D,k,dtype", PIPELINES,
+                         ids=[f"{p[0]}-{p[1]}-{p[6]}" for p in PIPELINES])
+def test_each_pipeline_exact_vs_oracle(gpu, sample, filt, Q, N, D, k, dtype):
+    """Every pair of passes the plan can choose, at a shape the plan's query says takes it:
+    bit-exact against the oracle on an integer grid with many exact ties, with a doc offset."""
+    from irc_amd import retrieval
+
+    rng = np.random.default_rng(Q * 13 + N + k)
+    q = _grid(rng, (Q, D), 3)
+    d = _grid(rng, (N, D), 3)
+    with _single_pass(filt == "gemm_lists"):
+        assert retrieval.scan_pipeline(Q, N, D, k, dtype) == (sample, filt, N)
+        if dtype == "e4m3":
+            q8, d8 = O.quantize_e4m3(q * 16), O.quantize_e4m3(d * 16)  # m / 8: e4m3-exact
+            assert np.array_equal(O.dequantize_e4m3(d8), d * 16)
+            s, i = retrieval.scan_topk_fp8(_dev(q8, gpu), _dev(d8, gpu), k, 9, 1.0 / 256)
+            ri, rs = O.scan_topk_fp8(q8, d8, k, doc_offset=9, score_scale=1.0 / 256)
+        else:
+            s, i = retrieval.scan_topk(_dev(q, gpu), _dev(d, gpu), k, 9)
+            ri, rs = O.scan_topk(q, d, k, doc_offset=9)
+    np.testing.assert_array_equal(i.cpu().numpy(), ri)
+    np.testing.assert_array_equal(s.cpu().numpy(), rs)
+
+
 def test_adversarial_sorted_corpus(gpu):
     """Later docs strictly better than the sample: nearly every doc survives the
     threshold, the selection must still be exact."""
@@ -145,14 +185,34 @@ def test_adversarial_sorted_corpus_gemm_filter(gpu):
 
 
 def test_adversarial_sorted_corpus_gemm_sample(gpu):
-    """Q = 300 (two query tiles): the sampled pipeline with its threshold sample on the
-    GEMM kernel (4-key lists per 256-doc sample tile, k-th of the lists): whole
-    regions survive the threshold, the selection must still be exact."""
+    """Q = 300 (two query tiles) on the GEMM-kernel filter.  At k = 100 the 3,334-doc sample
+    has 14 tiles of 256 = 56 list keys, fewer than 4 k, so the threshold sample runs on the
+    tile kernel (group maxima, radix select): whole regions survive the threshold, the
+    selection must still be exact.  (The name is kept; the k = 10 case below takes the GEMM
+    sample.)"""
+    from irc_amd import retrieval
+
     N, D, k = 50000, 128, 100
+    assert retrieval.scan_pipeline(300, N, D, k) == ("tile", "gemm_keys", N)
+    _check_sorted_corpus(gpu, _sorted_corpus_queries(D), N, D, k)
+
+
+def test_adversarial_sorted_corpus_gemm_sample_k10(gpu):
+    """The same corpus and queries at k = 10: 13 sample tiles = 52 list keys >= 4 k, so the
+    threshold sample runs on the GEMM kernel (4-key lists per 256-doc sample tile, k-th of
+    the lists)."""
+    from irc_amd import retrieval
+
+    N, D, k = 50000, 128, 10
+    assert retrieval.scan_pipeline(300, N, D, k) == ("gemm", "gemm_keys", N)
+    _check_sorted_corpus(gpu, _sorted_corpus_queries(D), N, D, k)
+
+
+def _sorted_corpus_queries(D):
     q = np.zeros((300, D), np.float32)
     q[:, 0] = 1.0
     q[::3, 1] = 0.5
-    _check_sorted_corpus(gpu, q, N, D, k)
+    return q
 
 
 def _check_sorted_corpus(gpu, q, N, D, k):
