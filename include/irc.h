@@ -403,6 +403,65 @@ int irc_ivf_search(const void* queries, const void* docs, const int32_t* row_id,
                    int64_t workspace_bytes, float* out_score, int64_t* out_idx, int32_t* out_n,
                    int32_t* out_probe, irc_stream_t stream);
 
+/* irc_ivf_topk over e4m3 lists: the same restricted dense scoring (src/evaluation.py:110-112
+ * over the probed lists' rows) on a shard stored at half the bytes, as irc_rerank_topk_fp8 is
+ * to irc_rerank_topk.  queries [Q, D] and docs [N, D] (in list order) are e4m3fn bytes as
+ * irc_quantize_fp8 writes them; every other array, the plan, the work item, the ranking, the
+ * padding and out_n are irc_ivf_topk's.  The raw score is the fp32 sum of the products of the
+ * decoded codes on v_mfma_f32_32x32x16_fp8_fp8 -- four k-slices of D / 4 bytes, each one chain
+ * in ascending k, added as (s0 + s1) + (s2 + s3) -- and the score reported and ranked by is
+ * that sum times score_scale, a power of two, so the product is exact.  One fixed order per
+ * (query, row): the same bits with other queries in the batch, other lists probed, another
+ * place of the list.  A NaN code ranks in no defined place.  Workspace: irc_ivf_topk_workspace
+ * (the keys do not depend on the element), every key written by the call.
+ *
+ * Validation, in this order, each IRC_E_INVALID with a message that starts "ivf_topk_fp8:" and
+ * found before any device work: no negative size; 1 <= k <= 1024; D as irc_scan_topk accepts;
+ * 1 <= nprobe <= nlist; score_scale a finite positive power of two; N < 2^31;
+ * Q * nprobe < 2^30; max_list_rows <= N and <= 65535 segments; then the workspace
+ * (IRC_E_WORKSPACE, required and given sizes in the message).  Q == 0 returns IRC_OK there and
+ * touches nothing; else no null array (docs may be null when N == 0) and queries / docs
+ * 16-byte aligned. */
+int irc_ivf_topk_fp8(const void* queries, const void* docs, const int32_t* row_id,
+                     const int64_t* list_off, int64_t nlist, const int32_t* probe,
+                     const int64_t* slot_off, const int64_t* cand_off, const int32_t* pair_order,
+                     const int64_t* seg_off, const int64_t* chunk_off, int64_t Q, int64_t nprobe,
+                     int64_t N, int64_t D, int64_t k, int64_t total_rows, int64_t max_list_rows,
+                     float score_scale, void* workspace, int64_t workspace_bytes,
+                     float* out_score, int64_t* out_idx, int32_t* out_n, irc_stream_t stream);
+
+/* irc_ivf_search over e4m3 lists: a whole cluster-pruned search of an fp8 shard in one
+ * stream-ordered call (no host synchronisation; it can be captured in a graph).  queries [Q, D]
+ * and centroids [nlist, D] are bf16, docs [N, D] e4m3fn bytes in list order.  On `stream`, in
+ * order: the probe exactly as irc_ivf_search runs it (irc_scan_topk of the bf16 queries over
+ * the bf16 centroids, skipped when probe is given -- so an e4m3 index probes the lists its bf16
+ * parent probes); irc_quantize_fp8 of the queries with query_scale into the workspace;
+ * irc_ivf_plan's kernels; irc_ivf_topk_fp8's scoring pass with score_scale; the select.  Same
+ * bits as irc_ivf_topk_fp8 over those codes and retrieval.ivf_plan's plan.
+ *
+ * Workspace (irc_ivf_search_fp8_workspace): irc_ivf_search_workspace's regions and
+ * align256(Q * 1024) bytes for the codes -- sized for the widest D, so D still does not enter.
+ * Contents before the call do not matter, and the slack of the key bound is never read.
+ * key_rows, max_list_rows and out_probe as for irc_ivf_search.
+ *
+ * Validation, in this order, each IRC_E_INVALID with a message that starts "ivf_search_fp8:"
+ * and found before any device work: no negative size; 1 <= k <= 1024; D as irc_scan_topk
+ * accepts; 1 <= nprobe <= nlist (and <= 1024 when the call probes itself); score_scale a
+ * finite positive power of two; query_scale finite and positive; N < 2^31; Q * nprobe < 2^30;
+ * max_list_rows <= N and <= 65535 segments; then the workspace (IRC_E_WORKSPACE, required and
+ * given sizes in the message).  Q == 0 returns IRC_OK there and touches nothing; else no null
+ * array (docs may be null when N == 0; one of probe and centroids is given) and queries, docs
+ * and centroids 16-byte aligned. */
+int64_t irc_ivf_search_fp8_workspace(int64_t Q, int64_t nprobe, int64_t nlist, int64_t key_rows,
+                                     int64_t k);
+int irc_ivf_search_fp8(const void* queries, const void* docs, const int32_t* row_id,
+                       const int64_t* list_off, int64_t nlist, const void* centroids,
+                       const int32_t* probe, int64_t Q, int64_t nprobe, int64_t N, int64_t D,
+                       int64_t k, int64_t key_rows, int64_t max_list_rows, float query_scale,
+                       float score_scale, void* workspace, int64_t workspace_bytes,
+                       float* out_score, int64_t* out_idx, int32_t* out_n, int32_t* out_probe,
+                       irc_stream_t stream);
+
 /* Raw score tile for tests / diagnostics: out[Q, N] fp32 = queries . docs^T
  * using the same MFMA path as irc_scan_topk. */
 int irc_scan_scores(const void* queries, const void* docs, int64_t Q, int64_t N, int64_t D,

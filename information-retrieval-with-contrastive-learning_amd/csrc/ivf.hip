@@ -34,6 +34,10 @@
 //    issues the probe, the plan's own kernels (irc_ivf_plan, below the scoring kernel), the
 //    scoring pass and the select on one stream with no host synchronisation, the key count
 //    replaced by a host bound.
+//  * e4m3 lists (irc_ivf_topk_fp8, irc_ivf_search_fp8): the same body on
+//    v_mfma_f32_32x32x16_fp8_fp8 over rows of D bytes; the plan, the work item, the slots and
+//    the select do not know the element.  irc_ivf_search_fp8 probes with the bf16 queries and
+//    scores their e4m3 codes, quantised into the workspace on the same stream.
 #include <stdint.h>
 
 #include "irc_common.h"
@@ -51,12 +55,44 @@ constexpr int XCH_LD = 65;          // floats per register row of the exchange (
 constexpr int XCH_WAVE = 16 * XCH_LD;
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-// LDS of one workgroup: the row tile (rows padded by 16 bytes: the fragment reads of 32 rows
-// then spread over the banks), the k-slice exchange, the chunk's 32 slot bases.
-template <int D>
+// The element forms of the scoring kernel.  EB = 2: bf16 rows on v_mfma_f32_32x32x16_bf16, a
+// lane's fragment of one k-step is 16 bytes.  EB = 1: e4m3fn bytes on
+// v_mfma_f32_32x32x16_fp8_fp8 (the instruction of the fp8 scan, scan_topk.hip EB = 1), a
+// lane's fragment is 8 bytes.  A k-step is 16 elements in both, so a wave's chain is D / 64
+// MFMAs whatever the element.
+template <int EB>
+struct Elem;
+template <>
+struct Elem<2> {
+  typedef u16x8 frag;
+  static __device__ __forceinline__ frag zero() { return u16x8{0, 0, 0, 0, 0, 0, 0, 0}; }
+  static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 acc) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
+                                                   __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
+  }
+};
+template <>
+struct Elem<1> {
+  typedef long frag;
+  static __device__ __forceinline__ frag zero() { return 0; }
+  static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 acc) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(a, b, acc, 0, 0, 0);
+  }
+};
+
+// LDS of one workgroup: the row tile, the k-slice exchange, the chunk's 32 slot bases.  The
+// rows are padded so that the fragment reads of 32 rows spread over the banks: by 16 bytes for
+// the 16-byte bf16 fragments, by 8 for the 8-byte e4m3 ones (row stride 8 x odd: 32 rows x 2
+// banks cover the 64 banks once).  The e4m3 tile is 32 rows too, half the bf16 tile's bytes: a
+// 64-row tile (two MFMA blocks and two accumulators per wave, the bf16 tile's bytes per pair of
+// barriers) was measured and lost -- its kernel ran at the bf16 kernel's time, not at half of
+// it ("e4m3 lists"; profiles/ivf_fp8_probe_tile64.json).
+template <int D, int EB = 2>
 struct Lds {
-  static constexpr int ROW_B = D * 2 + 16;
+  static constexpr int ROW_D = D * EB;  // bytes of a row in memory
+  static constexpr int ROW_B = ROW_D + 8 * EB;
   static constexpr int TILE_B = IVF_MT * ROW_B;
   static constexpr int XCH_AT = TILE_B;
   static constexpr int SLOT_AT = XCH_AT + IVF_KS * XCH_WAVE * 4;
@@ -65,16 +101,23 @@ struct Lds {
   static_assert(SLOT_AT % 8 == 0 && XCH_AT % 16 == 0, "alignment");
 };
 
-template <int D>
+// One body for both elements and all seven widths.  score_scale is the e4m3 form's descale
+// (a power of two: the multiply is exact); the bf16 form does not read it.
+template <int D, int EB = 2>
 __global__ __launch_bounds__(IVF_NT) void ivf_score_kernel(
-    const unsigned short* __restrict__ queries, const unsigned short* __restrict__ docs,
+    const unsigned char* __restrict__ queries, const unsigned char* __restrict__ docs,
     const int32_t* __restrict__ row_id, const int64_t* __restrict__ list_off, int nlist,
     const int64_t* __restrict__ slot_off, const int32_t* __restrict__ pair_order,
     const int64_t* __restrict__ seg_off, const int64_t* __restrict__ chunk_off, int nprobe,
-    int64_t n_pairs, int64_t N, int64_t n_keys, uint64_t* __restrict__ keys) {
-  typedef Lds<D> L;
-  constexpr int PASSES = D / 64;  // 16-byte pieces per thread per tile
+    int64_t n_pairs, int64_t N, int64_t n_keys, uint64_t* __restrict__ keys, float score_scale) {
+  typedef Lds<D, EB> L;
+  typedef Elem<EB> E;
+  typedef typename E::frag frag;
+  constexpr int TILE_D = IVF_MT * L::ROW_D;  // bytes of a tile in memory
+  constexpr int PASSES = (TILE_D + IVF_NT * 16 - 1) / (IVF_NT * 16);  // 16-byte pieces per thread
+  constexpr bool PART = TILE_D % (IVF_NT * 16) != 0;  // e4m3 at D = 64: half a pass
   constexpr int KSTEPS = D / 64;  // MFMAs per wave per tile (D / 4 over 16)
+  constexpr int FB = 8 * EB;      // bytes of a lane's fragment
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* xch = reinterpret_cast<float*>(smem + L::XCH_AT);
   int64_t* s_slot = reinterpret_cast<int64_t*>(smem + L::SLOT_AT);
@@ -106,16 +149,16 @@ __global__ __launch_bounds__(IVF_NT) void ivf_score_kernel(
 
   // the chunk's queries, gathered by index into this wave's k-slice of B fragments
   const int col = lane & 31, half = lane >> 5;
-  u16x8 bfr[KSTEPS];
+  frag bfr[KSTEPS];
   {
     int64_t pair = col < ncols ? (int64_t)pair_order[p0 + col] : -1;
     if (pair >= n_pairs) pair = -1;
-    const unsigned short* qp =
-        queries + (pair < 0 ? 0 : pair / nprobe) * D + wave * (D / IVF_KS) + 8 * half;
+    const unsigned char* qp = queries + (pair < 0 ? 0 : pair / nprobe) * L::ROW_D +
+                              wave * (L::ROW_D / IVF_KS) + FB * half;
 #pragma unroll
     for (int s = 0; s < KSTEPS; ++s) {
-      bfr[s] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (pair >= 0) bfr[s] = *reinterpret_cast<const u16x8*>(qp + 16 * s);
+      bfr[s] = E::zero();
+      if (pair >= 0) bfr[s] = *reinterpret_cast<const frag*>(qp + 2 * FB * s);
     }
     if (tid < IVF_CHUNK) {
       int64_t base = -1;
@@ -134,17 +177,24 @@ __global__ __launch_bounds__(IVF_NT) void ivf_score_kernel(
 #pragma unroll
     for (int p = 0; p < PASSES; ++p) {
       const int at = (p * IVF_NT + tid) * 16;
-      int64_t row = r0 + (int64_t)t * IVF_MT + at / (D * 2);
+      if (PART && at >= TILE_D) continue;
+      int64_t row = r0 + (int64_t)t * IVF_MT + at / L::ROW_D;
       row = row < rend ? row : rend - 1;
-      stage[p] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(docs) +
-                                                 row * (D * 2) + at % (D * 2));
+      stage[p] = *reinterpret_cast<const u32x4*>(docs + row * L::ROW_D + at % L::ROW_D);
     }
   };
   auto store_tile = [&]() {
 #pragma unroll
     for (int p = 0; p < PASSES; ++p) {
       const int at = (p * IVF_NT + tid) * 16;
-      *reinterpret_cast<u32x4*>(smem + (at / (D * 2)) * L::ROW_B + at % (D * 2)) = stage[p];
+      if (PART && at >= TILE_D) continue;
+      char* dst = smem + (at / L::ROW_D) * L::ROW_B + at % L::ROW_D;
+      if constexpr (EB == 2) {
+        *reinterpret_cast<u32x4*>(dst) = stage[p];
+      } else {  // the e4m3 row stride is a multiple of 8, not of 16
+        *reinterpret_cast<u32x2*>(dst) = u32x2{stage[p][0], stage[p][1]};
+        *reinterpret_cast<u32x2*>(dst + 8) = u32x2{stage[p][2], stage[p][3]};
+      }
     }
   };
 
@@ -159,14 +209,12 @@ __global__ __launch_bounds__(IVF_NT) void ivf_score_kernel(
 #pragma unroll 1
   for (int t = 0; t < nt; ++t) {
     if (t + 1 < nt) load_tile(t + 1);
-    const char* tile = smem + col * L::ROW_B + (wave * (D / IVF_KS) + 8 * half) * 2;
+    const char* tile = smem + col * L::ROW_B + wave * (L::ROW_D / IVF_KS) + FB * half;
     f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int s = 0; s < KSTEPS; ++s) {
-      const u16x8 av = *reinterpret_cast<const u16x8*>(tile + 32 * s);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av),
-                                                    __builtin_bit_cast(bf16x8, bfr[s]), acc, 0,
-                                                    0, 0);
+      const frag av = *reinterpret_cast<const frag*>(tile + 2 * FB * s);
+      acc = E::mfma(av, bfr[s], acc);
     }
     // acc[r]: row (r & 3) + 8 (r >> 2) + 4 half, column col, over this wave's k-slice
 #pragma unroll
@@ -180,7 +228,8 @@ __global__ __launch_bounds__(IVF_NT) void ivf_score_kernel(
       for (int j = 0; j < IVF_CHUNK / 8; ++j) {
         const int oc = ocol0 + 8 * j;
         const float* xp = xch + oat + oc;
-        const float sum = (xp[0] + xp[XCH_WAVE]) + (xp[2 * XCH_WAVE] + xp[3 * XCH_WAVE]);
+        float sum = (xp[0] + xp[XCH_WAVE]) + (xp[2 * XCH_WAVE] + xp[3 * XCH_WAVE]);
+        if constexpr (EB == 1) sum *= score_scale;
         const int64_t base = s_slot[oc];
         const int64_t at = base + (row - lstart);
         if (base >= 0 && at < n_keys) keys[at] = make_key(sum, gid);
@@ -535,29 +584,34 @@ static int plan_launch(const void* probe, bool probe_i64, const int64_t* list_of
   return check_launch("ivf_plan kernels");
 }
 
-// The tail both entries end in: the scoring pass over a plan and the select.  n_keys is the
+// The tail every entry ends in: the scoring pass over a plan and the select.  n_keys is the
 // key region's size: the plan's own total (irc_ivf_topk) or a host bound on it
-// (irc_ivf_search).
+// (irc_ivf_search).  eb = 2: bf16 operands; eb = 1: e4m3 bytes, the sums times score_scale.
 static int score_and_select(const void* queries, const void* docs, const int32_t* row_id,
                             const int64_t* list_off, int64_t nlist, const int64_t* slot_off,
                             const int64_t* cand_off, const int32_t* pair_order,
                             const int64_t* seg_off, const int64_t* chunk_off, int64_t Q,
                             int64_t nprobe, int64_t N, int64_t D, int64_t k, int64_t n_keys,
                             int64_t max_list_rows, uint64_t* keys, float* out_score,
-                            int64_t* out_idx, int32_t* out_n, hipStream_t st) {
+                            int64_t* out_idx, int32_t* out_n, hipStream_t st, int eb = 2,
+                            float score_scale = 1.0f) {
   const int64_t n_pairs = Q * nprobe;
   if (n_keys > 0 && max_list_rows > 0) {
     // every list has at most one partly filled chunk
     const int64_t gx = n_pairs / IVF_CHUNK + (nlist < n_pairs ? nlist : n_pairs);
     const int64_t gy = (max_list_rows + IVF_TILE_ROWS - 1) / IVF_TILE_ROWS;
-    const unsigned short* qp = static_cast<const unsigned short*>(queries);
-    const unsigned short* dp = static_cast<const unsigned short*>(docs);
+    const unsigned char* qp = static_cast<const unsigned char*>(queries);
+    const unsigned char* dp = static_cast<const unsigned char*>(docs);
     prof_begin(st);
-#define IRC_IVF_CASE(DD)                                                                       \
-  case DD:                                                                                     \
-    hipLaunchKernelGGL((ivf_score_kernel<DD>), dim3((unsigned)gx, (unsigned)gy), dim3(IVF_NT), \
-                       Lds<DD>::BYTES, st, qp, dp, row_id, list_off, (int)nlist, slot_off,     \
-                       pair_order, seg_off, chunk_off, (int)nprobe, n_pairs, N, n_keys, keys); \
+#define IRC_IVF_LAUNCH(DD, EB)                                                                   \
+  hipLaunchKernelGGL((ivf_score_kernel<DD, EB>), dim3((unsigned)gx, (unsigned)gy), dim3(IVF_NT), \
+                     (Lds<DD, EB>::BYTES), st, qp, dp, row_id, list_off, (int)nlist, slot_off,   \
+                     pair_order, seg_off, chunk_off, (int)nprobe, n_pairs, N, n_keys, keys,      \
+                     score_scale)
+#define IRC_IVF_CASE(DD)                   \
+  case DD:                                 \
+    if (eb == 2) IRC_IVF_LAUNCH(DD, 2);    \
+    else IRC_IVF_LAUNCH(DD, 1);            \
     break;
     switch (D) {
       IRC_IVF_CASE(64)
@@ -569,11 +623,12 @@ static int score_and_select(const void* queries, const void* docs, const int32_t
       default: IRC_IVF_CASE(1024)
     }
 #undef IRC_IVF_CASE
+#undef IRC_IVF_LAUNCH
     // The rows streamed are the sum over lists of chunks x rows, which only the device knows;
     // the host's figure is its upper bound, every pair streaming its list alone -- and from
     // irc_ivf_search a bound of that bound, n_keys being Q x the nprobe longest lists.
     // tools/ivf_probe.py reports the exact count from the plan.
-    prof_end("ivf_score", st, (double)n_keys * D * 2.0);
+    prof_end(eb == 2 ? "ivf_score" : "ivf_score_fp8", st, (double)n_keys * D * (double)eb);
     if (int rc = check_launch("ivf_score_kernel")) return rc;
   }
   return rerank::select_topk(keys, cand_off, n_keys, Q, (int)k, out_score, out_idx, out_n, st);
@@ -598,14 +653,23 @@ static int score_and_select(const void* queries, const void* docs, const int32_t
               "%s: max_list_rows=%lld above N or %lld", name, (long long)max_list_rows,          \
               65535ll * IVF_TILE_ROWS)
 
+// the e4m3 entries' scales, checked directly after nprobe
+#define IRC_IVF_CHECK_SCORE_SCALE(name) \
+  IRC_REQUIRE(pow2_scale(score_scale), "%s: score_scale must be a power of two", name)
+#define IRC_IVF_CHECK_QUERY_SCALE(name)                                                       \
+  IRC_REQUIRE(query_scale > 0.f && std::isfinite(query_scale),                                \
+              "%s: query_scale=%g must be finite and positive", name, (double)query_scale)
+
 constexpr int IVF_PROBE_MAX = 1024;  // the scan's largest k: the lists a call can probe itself
 
 // irc_ivf_search's workspace: the keys, the plan, its scratch, the probe's outputs and scan.
 struct SearchWs {
   size_t keys, slot_off, cand_off, pair_order, seg_off, chunk_off, scratch, probe_idx,
-      probe_score, scan, scan_bytes, bytes;
+      probe_score, scan, scan_bytes, codes, bytes;
 };
-static SearchWs search_ws(int64_t Q, int64_t nprobe, int64_t nlist, int64_t key_rows, int64_t k) {
+constexpr int64_t IVF_MAX_D = 1024;  // the widest row: the query codes' region does not know D
+static SearchWs search_ws(int64_t Q, int64_t nprobe, int64_t nlist, int64_t key_rows, int64_t k,
+                          bool fp8 = false) {
   (void)k;
   Q = Q > 0 ? Q : 0;
   nprobe = nprobe > 0 ? nprobe : 0;
@@ -629,7 +693,9 @@ static SearchWs search_ws(int64_t Q, int64_t nprobe, int64_t nlist, int64_t key_
       const int64_t b = irc_scan_topk_workspace(Q, nlist, d, nprobe);
       w.scan_bytes = (size_t)b > w.scan_bytes ? (size_t)b : w.scan_bytes;
     }
-  w.bytes = w.scan + align256(w.scan_bytes);
+  // irc_ivf_search_fp8 only: the queries' e4m3 codes
+  w.codes = w.scan + align256(w.scan_bytes);
+  w.bytes = w.codes + (fp8 ? align256((size_t)Q * (size_t)IVF_MAX_D) : 0);
   return w;
 }
 
@@ -681,18 +747,19 @@ extern "C" int64_t irc_ivf_topk_workspace(int64_t Q, int64_t nprobe, int64_t tot
   return (int64_t)workspace_bytes_for(total_rows);
 }
 
-// The order of the checks is part of the interface (tests/test_ivf_cpu.py): a call that breaks
-// two reports the earlier one.
-extern "C" int irc_ivf_topk(const void* queries, const void* docs, const int32_t* row_id,
-                            const int64_t* list_off, int64_t nlist, const int32_t* probe,
-                            const int64_t* slot_off, const int64_t* cand_off,
-                            const int32_t* pair_order, const int64_t* seg_off,
-                            const int64_t* chunk_off, int64_t Q, int64_t nprobe, int64_t N,
-                            int64_t D, int64_t k, int64_t total_rows, int64_t max_list_rows,
-                            void* workspace, int64_t workspace_bytes, float* out_score,
-                            int64_t* out_idx, int32_t* out_n, irc_stream_t stream) {
-  const char* name = "ivf_topk";
+// irc_ivf_topk (eb = 2) and irc_ivf_topk_fp8 (eb = 1) in one validated path.  The order of the
+// checks is part of the interface (tests/test_ivf_cpu.py, tests/test_ivf_fp8_cpu.py): a call
+// that breaks two reports the earlier one; the e4m3 form's scale comes directly after nprobe.
+static int topk_impl(const char* name, int eb, float score_scale, const void* queries,
+                     const void* docs, const int32_t* row_id, const int64_t* list_off,
+                     int64_t nlist, const int32_t* probe, const int64_t* slot_off,
+                     const int64_t* cand_off, const int32_t* pair_order, const int64_t* seg_off,
+                     const int64_t* chunk_off, int64_t Q, int64_t nprobe, int64_t N, int64_t D,
+                     int64_t k, int64_t total_rows, int64_t max_list_rows, void* workspace,
+                     int64_t workspace_bytes, float* out_score, int64_t* out_idx, int32_t* out_n,
+                     irc_stream_t stream) {
   IRC_IVF_CHECK_SIZES(name, total_rows);
+  if (eb == 1) IRC_IVF_CHECK_SCORE_SCALE(name);
   IRC_IVF_CHECK_RANGES(name);
   const int64_t need = (int64_t)workspace_bytes_for(total_rows);
   if (workspace == nullptr || workspace_bytes < need) {
@@ -709,7 +776,35 @@ extern "C" int irc_ivf_topk(const void* queries, const void* docs, const int32_t
   return score_and_select(queries, docs, row_id, list_off, nlist, slot_off, cand_off, pair_order,
                           seg_off, chunk_off, Q, nprobe, N, D, k, total_rows, max_list_rows,
                           static_cast<uint64_t*>(workspace), out_score, out_idx, out_n,
-                          as_stream(stream));
+                          as_stream(stream), eb, score_scale);
+}
+
+extern "C" int irc_ivf_topk(const void* queries, const void* docs, const int32_t* row_id,
+                            const int64_t* list_off, int64_t nlist, const int32_t* probe,
+                            const int64_t* slot_off, const int64_t* cand_off,
+                            const int32_t* pair_order, const int64_t* seg_off,
+                            const int64_t* chunk_off, int64_t Q, int64_t nprobe, int64_t N,
+                            int64_t D, int64_t k, int64_t total_rows, int64_t max_list_rows,
+                            void* workspace, int64_t workspace_bytes, float* out_score,
+                            int64_t* out_idx, int32_t* out_n, irc_stream_t stream) {
+  return topk_impl("ivf_topk", 2, 1.0f, queries, docs, row_id, list_off, nlist, probe, slot_off,
+                   cand_off, pair_order, seg_off, chunk_off, Q, nprobe, N, D, k, total_rows,
+                   max_list_rows, workspace, workspace_bytes, out_score, out_idx, out_n, stream);
+}
+
+extern "C" int irc_ivf_topk_fp8(const void* queries, const void* docs, const int32_t* row_id,
+                                const int64_t* list_off, int64_t nlist, const int32_t* probe,
+                                const int64_t* slot_off, const int64_t* cand_off,
+                                const int32_t* pair_order, const int64_t* seg_off,
+                                const int64_t* chunk_off, int64_t Q, int64_t nprobe, int64_t N,
+                                int64_t D, int64_t k, int64_t total_rows, int64_t max_list_rows,
+                                float score_scale, void* workspace, int64_t workspace_bytes,
+                                float* out_score, int64_t* out_idx, int32_t* out_n,
+                                irc_stream_t stream) {
+  return topk_impl("ivf_topk_fp8", 1, score_scale, queries, docs, row_id, list_off, nlist, probe,
+                   slot_off, cand_off, pair_order, seg_off, chunk_off, Q, nprobe, N, D, k,
+                   total_rows, max_list_rows, workspace, workspace_bytes, out_score, out_idx,
+                   out_n, stream);
 }
 
 extern "C" int64_t irc_ivf_search_workspace(int64_t Q, int64_t nprobe, int64_t nlist,
@@ -717,22 +812,32 @@ extern "C" int64_t irc_ivf_search_workspace(int64_t Q, int64_t nprobe, int64_t n
   return (int64_t)search_ws(Q, nprobe, nlist, key_rows, k).bytes;
 }
 
-// The order of the checks is part of the interface (tests/test_ivf_native_cpu.py): irc_ivf_topk's,
-// with the probe's own limit after nprobe's and the centroids among the pointers.
-extern "C" int irc_ivf_search(const void* queries, const void* docs, const int32_t* row_id,
-                              const int64_t* list_off, int64_t nlist, const void* centroids,
-                              const int32_t* probe, int64_t Q, int64_t nprobe, int64_t N,
-                              int64_t D, int64_t k, int64_t key_rows, int64_t max_list_rows,
-                              void* workspace, int64_t workspace_bytes, float* out_score,
-                              int64_t* out_idx, int32_t* out_n, int32_t* out_probe,
-                              irc_stream_t stream) {
-  const char* name = "ivf_search";
+extern "C" int64_t irc_ivf_search_fp8_workspace(int64_t Q, int64_t nprobe, int64_t nlist,
+                                                int64_t key_rows, int64_t k) {
+  return (int64_t)search_ws(Q, nprobe, nlist, key_rows, k, true).bytes;
+}
+
+// irc_ivf_search (eb = 2) and irc_ivf_search_fp8 (eb = 1) in one validated path.  The order of
+// the checks is part of the interface (tests/test_ivf_native_cpu.py, tests/test_ivf_fp8_cpu.py):
+// irc_ivf_topk's, with the probe's own limit after nprobe's, then the e4m3 form's two scales,
+// and the centroids among the pointers.
+static int search_impl(const char* name, int eb, float query_scale, float score_scale,
+                       const void* queries, const void* docs, const int32_t* row_id,
+                       const int64_t* list_off, int64_t nlist, const void* centroids,
+                       const int32_t* probe, int64_t Q, int64_t nprobe, int64_t N, int64_t D,
+                       int64_t k, int64_t key_rows, int64_t max_list_rows, void* workspace,
+                       int64_t workspace_bytes, float* out_score, int64_t* out_idx,
+                       int32_t* out_n, int32_t* out_probe, irc_stream_t stream) {
   IRC_IVF_CHECK_SIZES(name, key_rows);
   IRC_REQUIRE(probe != nullptr || nprobe <= IVF_PROBE_MAX,
               "%s: nprobe=%lld above %d, the most lists a call probes itself", name,
               (long long)nprobe, IVF_PROBE_MAX);
+  if (eb == 1) {
+    IRC_IVF_CHECK_SCORE_SCALE(name);
+    IRC_IVF_CHECK_QUERY_SCALE(name);
+  }
   IRC_IVF_CHECK_RANGES(name);
-  const SearchWs w = search_ws(Q, nprobe, nlist, key_rows, k);
+  const SearchWs w = search_ws(Q, nprobe, nlist, key_rows, k, eb == 1);
   if (workspace == nullptr || workspace_bytes < (int64_t)w.bytes) {
     set_error("%s: workspace %lld < required %lld bytes", name, (long long)workspace_bytes,
               (long long)w.bytes);
@@ -763,11 +868,42 @@ extern "C" int irc_ivf_search(const void* queries, const void* docs, const int32
       return rc;
     pr = ids;
   }
+  const void* scored = queries;
+  if (eb == 1) {
+    // the probe ranked the bf16 queries; the lists are scored against their e4m3 codes
+    if (int rc = irc_quantize_fp8(0, queries, Q * D, query_scale, ws + w.codes, stream)) return rc;
+    scored = ws + w.codes;
+  }
   if (int rc = plan_launch(pr, probe == nullptr, list_off, Q, nprobe, nlist, ws + w.scratch,
                            slot_off, cand_off, pair_order, seg_off, chunk_off, out_probe, st))
     return rc;
-  return score_and_select(queries, docs, row_id, list_off, nlist, slot_off, cand_off, pair_order,
+  return score_and_select(scored, docs, row_id, list_off, nlist, slot_off, cand_off, pair_order,
                           seg_off, chunk_off, Q, nprobe, N, D, k, key_rows, max_list_rows,
-                          reinterpret_cast<uint64_t*>(ws + w.keys), out_score, out_idx, out_n,
-                          st);
+                          reinterpret_cast<uint64_t*>(ws + w.keys), out_score, out_idx, out_n, st,
+                          eb, score_scale);
+}
+
+extern "C" int irc_ivf_search(const void* queries, const void* docs, const int32_t* row_id,
+                              const int64_t* list_off, int64_t nlist, const void* centroids,
+                              const int32_t* probe, int64_t Q, int64_t nprobe, int64_t N,
+                              int64_t D, int64_t k, int64_t key_rows, int64_t max_list_rows,
+                              void* workspace, int64_t workspace_bytes, float* out_score,
+                              int64_t* out_idx, int32_t* out_n, int32_t* out_probe,
+                              irc_stream_t stream) {
+  return search_impl("ivf_search", 2, 1.0f, 1.0f, queries, docs, row_id, list_off, nlist,
+                     centroids, probe, Q, nprobe, N, D, k, key_rows, max_list_rows, workspace,
+                     workspace_bytes, out_score, out_idx, out_n, out_probe, stream);
+}
+
+extern "C" int irc_ivf_search_fp8(const void* queries, const void* docs, const int32_t* row_id,
+                                  const int64_t* list_off, int64_t nlist, const void* centroids,
+                                  const int32_t* probe, int64_t Q, int64_t nprobe, int64_t N,
+                                  int64_t D, int64_t k, int64_t key_rows, int64_t max_list_rows,
+                                  float query_scale, float score_scale, void* workspace,
+                                  int64_t workspace_bytes, float* out_score, int64_t* out_idx,
+                                  int32_t* out_n, int32_t* out_probe, irc_stream_t stream) {
+  return search_impl("ivf_search_fp8", 1, query_scale, score_scale, queries, docs, row_id,
+                     list_off, nlist, centroids, probe, Q, nprobe, N, D, k, key_rows,
+                     max_list_rows, workspace, workspace_bytes, out_score, out_idx, out_n,
+                     out_probe, stream);
 }

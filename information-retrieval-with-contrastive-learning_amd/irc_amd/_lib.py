@@ -69,6 +69,11 @@ SIGNATURES = {
     "irc_ivf_search_workspace": (I64, [I64, I64, I64, I64, I64]),
     "irc_ivf_search": (I32, [P, P, P, P, I64, P, P, I64, I64, I64, I64, I64, I64, I64, P, I64, P,
                              P, P, P, P]),
+    "irc_ivf_topk_fp8": (I32, [P, P, P, P, I64, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64,
+                               I64, F32, P, I64, P, P, P, P]),
+    "irc_ivf_search_fp8_workspace": (I64, [I64, I64, I64, I64, I64]),
+    "irc_ivf_search_fp8": (I32, [P, P, P, P, I64, P, P, I64, I64, I64, I64, I64, I64, I64, F32,
+                                 F32, P, I64, P, P, P, P, P]),
     "irc_scan_topk_fp8_workspace": (I64, [I64, I64, I64, I64]),
     "irc_scan_topk_fp8": (I32, [P, P, I64, I64, I64, I64, I64, F32, P, I64, P, P, P]),
     "irc_scan_scores_fp8": (I32, [P, P, I64, I64, I64, P, P]),

@@ -20,7 +20,9 @@ Cluster-pruned search: ``IVFDenseIndex`` keeps a shard clustered into lists and 
 exactly, only the rows of the lists nearest to each query; sharded as the scan is, each shard
 probing its own lists.  A search is one stream-ordered native call (``ivf_search``: probe, the
 plan built on the device, scoring, select); ``ivf_plan`` + ``ivf_topk`` are the same search with
-the plan built in torch, the documented form and the oracle of the native one.
+the plan built in torch, the documented form and the oracle of the native one.  The lists can
+be e4m3 bytes (``IVFDenseIndex.to_fp8``; ``ivf_search_fp8`` / ``ivf_topk_fp8``): the probe stays
+bf16, the queries are quantised inside the call.
 """
 from __future__ import annotations
 
@@ -705,9 +707,29 @@ def ivf_topk(queries: torch.Tensor, docs: torch.Tensor, row_id: torch.Tensor,
     The workspace holds one key per (pair, row).  Their total is read from the plan with ONE
     host synchronisation, as ``expand_ranges`` reads its row count, unless the caller passes
     ``total_rows`` (an upper bound), which keeps the call stream-ordered."""
+    return _ivf_topk_call(queries, docs, row_id, list_off, probe, k, max_list_rows, ws_tag,
+                          total_rows, None)
+
+
+def ivf_topk_fp8(queries: torch.Tensor, docs: torch.Tensor, row_id: torch.Tensor,
+                 list_off: torch.Tensor, probe: torch.Tensor, k: int, max_list_rows: int,
+                 score_scale: float = 1.0, ws_tag: str = "ivf", total_rows=None):
+    """``ivf_topk`` over e4m3 lists (irc_ivf_topk_fp8): queries [Q, D] and ``docs`` [N, D] (in
+    list order) are e4m3 bytes (uint8, see ``quantize_fp8``), everything else as there.  The
+    scores are the fp32 sums of the decoded codes' products times ``score_scale`` (a power of
+    two), one fixed order per (query, row)."""
+    _require_e4m3(queries, docs)  # a wrong dtype is a TypeError on any device
+    return _ivf_topk_call(queries, docs, row_id, list_off, probe, k, max_list_rows, ws_tag,
+                          total_rows, float(score_scale))
+
+
+def _ivf_topk_call(queries, docs, row_id, list_off, probe, k, max_list_rows, ws_tag, total_rows,
+                   score_scale):
+    """``ivf_topk`` (score_scale None: bf16 operands) and ``ivf_topk_fp8`` in one path."""
     require_hip(queries, docs, row_id, list_off, probe)
-    q = contig(queries, torch.bfloat16)
-    d = contig(docs, torch.bfloat16)
+    elem = torch.bfloat16 if score_scale is None else torch.uint8
+    q = contig(queries, elem)
+    d = contig(docs, elem)
     if d.shape[1] != q.shape[1]:
         raise ValueError(f"dim mismatch: queries D={q.shape[1]}, docs D={d.shape[1]}")
     if probe.dim() != 2 or probe.shape[0] != q.shape[0]:
@@ -729,10 +751,12 @@ def ivf_topk(queries: torch.Tensor, docs: torch.Tensor, row_id: torch.Tensor,
     out_n = torch.empty((Q,), dtype=torch.int32, device=q.device)
     nbytes = int(_lib.fn("irc_ivf_topk_workspace")(Q, nprobe, int(total_rows), k))
     ws = workspace(nbytes, q.device, ws_tag)
-    _lib.call("irc_ivf_topk", ptr(q), ptr(d), ptr(rid), ptr(lo), lo.numel() - 1, ptr(pr),
-              ptr(plan["slot_off"]), ptr(plan["cand_off"]), ptr(plan["pair_order"]),
-              ptr(plan["seg_off"]), ptr(plan["chunk_off"]), Q, nprobe, N, D, k, int(total_rows),
-              int(max_list_rows), ptr(ws), ws.numel(), ptr(out_s), ptr(out_i), ptr(out_n),
+    scale = () if score_scale is None else (score_scale,)
+    _lib.call("irc_ivf_topk" if score_scale is None else "irc_ivf_topk_fp8", ptr(q), ptr(d),
+              ptr(rid), ptr(lo), lo.numel() - 1, ptr(pr), ptr(plan["slot_off"]),
+              ptr(plan["cand_off"]), ptr(plan["pair_order"]), ptr(plan["seg_off"]),
+              ptr(plan["chunk_off"]), Q, nprobe, N, D, k, int(total_rows), int(max_list_rows),
+              *scale, ptr(ws), ws.numel(), ptr(out_s), ptr(out_i), ptr(out_n),
               stream_ptr(q.device))
     return out_s, out_i, out_n
 
@@ -785,6 +809,31 @@ def ivf_search(queries: torch.Tensor, docs: torch.Tensor, row_id: torch.Tensor,
     int64, n [Q] int32), contiguous, is written in place when given; ``out_probe`` int32
     [Q, nprobe] receives the probe that was used; ``ws`` is the caller's own workspace (uint8,
     at least irc_ivf_search_workspace bytes) instead of the cached one."""
+    return _ivf_search_call(queries, docs, row_id, list_off, k, key_rows, max_list_rows,
+                            centroids, nprobe, probe, ws_tag, out, out_probe, ws, None)
+
+
+def ivf_search_fp8(queries: torch.Tensor, docs: torch.Tensor, row_id: torch.Tensor,
+                   list_off: torch.Tensor, k: int, key_rows: int, max_list_rows: int,
+                   centroids=None, nprobe=None, probe=None, query_scale: float = FP8_SCALE,
+                   score_scale: float = 1.0 / (FP8_SCALE * FP8_SCALE), ws_tag: str = "ivf",
+                   out=None, out_probe=None, ws=None):
+    """``ivf_search`` over e4m3 lists in one native call (irc_ivf_search_fp8): ``queries``
+    [Q, D] and ``centroids`` are bf16, ``docs`` [N, D] e4m3 bytes (uint8) in list order.  The
+    probe is ``ivf_search``'s (bf16 queries over bf16 centroids), the queries are then
+    quantised with ``query_scale`` on the same stream and the lists scored against the codes,
+    the sums times ``score_scale`` (a power of two).  Same bits as ``ivf_topk_fp8`` of
+    ``quantize_fp8(queries, query_scale)``; every other argument as for ``ivf_search`` (``ws``:
+    at least irc_ivf_search_fp8_workspace bytes)."""
+    _require_e4m3(docs)  # a wrong dtype is a TypeError on any device
+    return _ivf_search_call(queries, docs, row_id, list_off, k, key_rows, max_list_rows,
+                            centroids, nprobe, probe, ws_tag, out, out_probe, ws,
+                            (float(query_scale), float(score_scale)))
+
+
+def _ivf_search_call(queries, docs, row_id, list_off, k, key_rows, max_list_rows, centroids,
+                     nprobe, probe, ws_tag, out, out_probe, ws, scales):
+    """``ivf_search`` (scales None: bf16 lists) and ``ivf_search_fp8`` in one path."""
     if queries.dim() != 2 or docs.dim() != 2 or docs.shape[1] != queries.shape[1]:
         raise ValueError(f"dim mismatch: queries {tuple(queries.shape)}, docs "
                          f"{tuple(docs.shape)}")
@@ -814,7 +863,7 @@ def ivf_search(queries: torch.Tensor, docs: torch.Tensor, row_id: torch.Tensor,
         raise ValueError(f"out_probe must be contiguous int32 [{Q}, {nprobe}]")
     require_hip(queries, docs, row_id, list_off, centroids, probe)
     q = contig(queries, torch.bfloat16)
-    d = contig(docs, torch.bfloat16)
+    d = contig(docs, torch.bfloat16 if scales is None else torch.uint8)
     rid = contig(row_id, torch.int32)
     lo = contig(list_off, torch.int64)
     pr = None if probe is None else contig(probe, torch.int32)
@@ -823,11 +872,12 @@ def ivf_search(queries: torch.Tensor, docs: torch.Tensor, row_id: torch.Tensor,
         out = (torch.empty((Q, k), dtype=torch.float32, device=q.device),
                torch.empty((Q, k), dtype=torch.int64, device=q.device),
                torch.empty((Q,), dtype=torch.int32, device=q.device))
-    nbytes = int(_lib.fn("irc_ivf_search_workspace")(Q, nprobe, nlist, int(key_rows), k))
+    entry = "irc_ivf_search" if scales is None else "irc_ivf_search_fp8"
+    nbytes = int(_lib.fn(entry + "_workspace")(Q, nprobe, nlist, int(key_rows), k))
     if ws is None:
         ws = workspace(nbytes, q.device, ws_tag)
-    _lib.call("irc_ivf_search", ptr(q), ptr(d), ptr(rid), ptr(lo), nlist, ptr(cen), ptr(pr), Q,
-              nprobe, N, D, k, int(key_rows), int(max_list_rows), ptr(ws), ws.numel(),
+    _lib.call(entry, ptr(q), ptr(d), ptr(rid), ptr(lo), nlist, ptr(cen), ptr(pr), Q, nprobe, N,
+              D, k, int(key_rows), int(max_list_rows), *(scales or ()), ptr(ws), ws.numel(),
               ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out_probe), stream_ptr(q.device))
     return out
 
@@ -1356,10 +1406,18 @@ class IVFDenseIndex(ShardedDenseIndex):
     its probed lists, by (score desc, global id asc), padding (-inf, -1), n[q] = min(k, rows in
     the probed lists).  With ``nprobe == nlist`` it is ``ShardedDenseIndex.search``'s ranking.
     Ids are global ids of the ORIGINAL corpus (``doc_offset`` + original row), so per-shard
-    results merge with ``topk_merge`` as the scan's do.  bf16 only.
+    results merge with ``topk_merge`` as the scan's do.
 
-    Attributes: ``docs`` [N, D] bf16, the rows in list order (the only copy); ``row_id`` int32
-    [N], each row's global id; ``list_off`` int64 [nlist + 1]; ``centroids`` [nlist, D] bf16;
+    ``dtype`` is "bf16" or, from ``to_fp8`` / ``train(dtype="fp8")`` / a loaded e4m3 shard,
+    "fp8": the lists are then e4m3 bytes (half the bytes a search streams), a search quantises
+    its queries with ``fp8_scale`` inside the native call and the scores are those of the
+    quantised embeddings, descaled exactly, as ``ShardedDenseIndex(dtype="fp8")`` reports them.
+    The centroids and the probe stay bf16, so an fp8 index probes the lists its bf16 parent
+    probes.
+
+    Attributes: ``docs`` [N, D] bf16 (or uint8 e4m3 bytes), the rows in list order (the only
+    copy); ``row_id`` int32 [N], each row's global id; ``list_off`` int64 [nlist + 1];
+    ``centroids`` [nlist, D] bf16;
     ``max_list_rows`` (host int, the longest list); ``max_workspace_bytes`` (the workspace one
     native call may take; a larger batch runs in query chunks, same bits).
 
@@ -1395,7 +1453,8 @@ class IVFDenseIndex(ShardedDenseIndex):
                    doc_offset: int = 0, group=None, dtype: str = "bf16"):
         """The index over a caller's clustering: ``assign`` [N] gives each row of ``docs`` its
         list in [0, nlist), ``centroids`` [nlist, D] is what ``probe`` ranks the lists by (inner
-        product).  One host synchronisation (the longest lists' lengths, ``key_bound``)."""
+        product).  One host synchronisation (the longest lists' lengths, ``key_bound``).
+        The lists are built from bf16 rows; ``to_fp8`` of the result stores them as e4m3."""
         if dtype != "bf16":
             raise ValueError(f"IVFDenseIndex is bf16 only (e4m3 lists are a follow-up), not "
                              f"dtype={dtype!r}")
@@ -1422,18 +1481,19 @@ class IVFDenseIndex(ShardedDenseIndex):
 
     @classmethod
     def train(cls, docs: torch.Tensor, nlist: int, doc_offset: int = 0, group=None,
-              niter: int = 20, nredo: int = 1, seed: int = 0, dtype: str = "bf16"):
+              niter: int = 20, nredo: int = 1, seed: int = 0, dtype: str = "bf16",
+              fp8_scale: float = FP8_SCALE):
         """Cluster ``docs`` [N, D] into ``nlist`` lists and build the index: ``cluster.kmeans`` on
         the fp32 rows, the centroids L2-normalised as the reference's run_kmeans leaves its
         prototypes (src/contrastor/utils.py:98), then every row assigned to the centroid of
         LARGEST INNER PRODUCT -- the probe ranks lists by inner product, so the assignment
         does too (``cluster._assign`` over the normalised centroids with a zero bias).  The
-        centroids are kept as bf16.  Under a launcher each rank trains over its own shard."""
+        centroids are kept as bf16.  Under a launcher each rank trains over its own shard.
+        ``dtype="fp8"`` trains the same way and returns ``.to_fp8(fp8_scale)``."""
         from . import cluster
 
-        if dtype != "bf16":
-            raise ValueError(f"IVFDenseIndex is bf16 only (e4m3 lists are a follow-up), not "
-                             f"dtype={dtype!r}")
+        if dtype not in ("bf16", "fp8"):
+            raise ValueError(f"dtype must be 'bf16' or 'fp8', not {dtype!r}")
         require_hip(docs)
         x = docs.float().contiguous()
         c, _, _ = cluster.kmeans(x, nlist, niter=niter, nredo=nredo, seed=seed)
@@ -1441,7 +1501,21 @@ class IVFDenseIndex(ShardedDenseIndex):
         c = torch.nn.functional.normalize(c, dim=1).to(torch.bfloat16)
         bias = torch.zeros((nlist,), dtype=torch.float32, device=x.device)
         assign, _ = cluster._assign(x, c.float().contiguous(), bias)
-        return cls.from_lists(docs, c, assign, doc_offset, group)
+        index = cls.from_lists(docs, c, assign, doc_offset, group)
+        return index if dtype == "bf16" else index.to_fp8(fp8_scale)
+
+    def to_fp8(self, fp8_scale: float = FP8_SCALE):
+        """A new index over the same clustering with e4m3 lists: ``docs`` is ``quantize_fp8`` of
+        this index's rows (already in list order) at ``fp8_scale``; ``row_id``, ``list_off``,
+        ``centroids`` and the key bounds are shared with this one.  No host synchronisation."""
+        if self.dtype != "bf16":
+            raise ValueError(f"to_fp8: the lists are already {self.dtype}")
+        other = type(self).__new__(type(self))
+        other.__dict__.update(self.__dict__)
+        other.dtype = "fp8"
+        other.fp8_scale = float(fp8_scale)
+        other.docs = quantize_fp8(self.docs, other.fp8_scale)
+        return other
 
     # ------------------------------------------------------------ persistence
     def save(self, directory: str, rank: int = 0, doc_ids=None) -> None:
@@ -1463,8 +1537,6 @@ class IVFDenseIndex(ShardedDenseIndex):
         import numpy as np
 
         self, doc_dict = super().load(directory, rank, device, group)
-        if self.dtype != "bf16":
-            raise ValueError(f"IVFDenseIndex is bf16 only, the saved shard is {self.dtype}")
         dev = self.docs.device
         with np.load(os.path.join(directory, f"ivf_{rank}.npz")) as z:
             self.centroids = torch.from_numpy(z["centroids"]).to(dev).view(torch.bfloat16)
@@ -1502,7 +1574,12 @@ class IVFDenseIndex(ShardedDenseIndex):
         else:  # a caller's wider probe: none of the other lists is longer than the last one kept
             bound = self._key_prefix[-1] + (nprobe - kept) * (
                 self._key_prefix[-1] - self._key_prefix[-2])
-        need = _lib.fn("irc_ivf_search_workspace")
+        fp8 = self.dtype == "fp8"
+        need = _lib.fn("irc_ivf_search_fp8_workspace" if fp8 else "irc_ivf_search_workspace")
+        # the descale ShardedDenseIndex(dtype="fp8").search applies
+        scales = dict(query_scale=self.fp8_scale,
+                      score_scale=1.0 / (self.fp8_scale * self.fp8_scale)) if fp8 else {}
+        search = ivf_search_fp8 if fp8 else ivf_search
         step = ivf_query_chunk(Q, self.max_workspace_bytes,
                                lambda c: int(need(c, nprobe, nlist, c * bound, k)))
         out = (torch.empty((Q, k), dtype=torch.float32, device=queries.device),
@@ -1510,11 +1587,11 @@ class IVFDenseIndex(ShardedDenseIndex):
                torch.empty((Q,), dtype=torch.int32, device=queries.device))
         for lo in range(0, max(Q, 1), max(step, 1)):
             hi = min(Q, lo + step)
-            ivf_search(queries[lo:hi], self.docs, self.row_id, self.list_off, k,
-                       (hi - lo) * bound, self.max_list_rows, centroids=self.centroids,
-                       nprobe=nprobe if probe is None else None,
-                       probe=None if probe is None else probe[lo:hi], ws_tag=ws_tag,
-                       out=tuple(o[lo:hi] for o in out))
+            search(queries[lo:hi], self.docs, self.row_id, self.list_off, k,
+                   (hi - lo) * bound, self.max_list_rows, centroids=self.centroids,
+                   nprobe=nprobe if probe is None else None,
+                   probe=None if probe is None else probe[lo:hi], ws_tag=ws_tag,
+                   out=tuple(o[lo:hi] for o in out), **scales)
         return out
 
     def search(self, queries: torch.Tensor, k: int, nprobe=None, probe=None,

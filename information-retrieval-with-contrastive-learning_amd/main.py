@@ -5,7 +5,7 @@
                    [--seed 1337] [--logdir log] [--ckptdir ckpt] [--retrieval sparse|dense|hybrid]
                    [--rerank-method auto|gather|stream] [--rerank-unit line|page]
                    [--index-dtype bf16|fp8] [--index flat|ivf] [--nlist N] [--nprobe P]
-                   [--fusion-weight W]
+                   [--ivf-list-dtype bf16|fp8] [--fusion-weight W]
 
 Multi-GPU (one process per GPU):
     torchrun --nproc-per-node N --master-addr 127.0.0.1 main.py [same flags]
@@ -25,7 +25,8 @@ k best pages, each by its best line, instead of the k best lines.  ``--fusion-we
 (hybrid only) ranks by the fused score dense + W * the claim's max-normalised TF-IDF page score.
 ``--index ivf`` (dense only) clusters the evidence corpus into ``--nlist`` lists and scores
 only the ``--nprobe`` lists nearest to each claim -- exactly, so what it trades for speed is
-which lists are looked at.  The compute runs on the MI355X HIP kernels only:
+which lists are looked at; ``--ivf-list-dtype fp8`` keeps those lists as e4m3 bytes (half the
+bytes a search streams; the probe stays bf16).  The compute runs on the MI355X HIP kernels only:
 ``--gpu -1`` (CPU) is rejected -- there is no CPU fallback in this build.
 """
 import argparse
@@ -95,6 +96,11 @@ def get_args(argv=None):
                    help="--index ivf: lists the corpus (each rank's slice) is clustered into")
     p.add_argument("--nprobe", default=8, type=int,
                    help="--index ivf: lists probed per claim (per shard), 1 .. min(nlist, 1024)")
+    p.add_argument("--ivf-list-dtype", default="bf16", type=str, choices=["bf16", "fp8"],
+                   help="--index ivf: how the lists' rows are kept in HBM. bf16 (default), or "
+                        "fp8: e4m3 bytes at half the size, the claims quantised inside the "
+                        "search call and the scores those of the quantised embeddings; the "
+                        "centroids and the probe stay bf16, so the same lists are probed")
     p.add_argument("--fusion-weight", default=0.0, type=float,
                    help="--retrieval hybrid: rank each candidate line by dense + W * sparse, "
                         "sparse being the claim's TF-IDF score of the line's page divided by "
@@ -108,6 +114,9 @@ def get_args(argv=None):
     if args.fusion_weight > 0 and args.retrieval != "hybrid":
         p.error("--fusion-weight fuses the sparse filter's score into the dense rerank: it "
                 "goes with --retrieval hybrid only")
+    if args.ivf_list_dtype != "bf16" and args.index != "ivf":
+        p.error("--ivf-list-dtype is the dtype of an IVF index's lists: it goes with --index "
+                "ivf only (a flat index takes --index-dtype)")
     if args.index == "ivf":
         if args.retrieval == "hybrid":
             p.error("--index ivf ranks the probed lists, not a candidate filter's rows: it "
@@ -116,7 +125,8 @@ def get_args(argv=None):
             p.error("--index ivf has no per-page unit yet (the rows are permuted): use "
                     "--rerank-unit line")
         if args.index_dtype == "fp8":
-            p.error("--index ivf keeps bf16 lists only: use --index-dtype bf16")
+            p.error("--index ivf takes --index-dtype bf16 only: e4m3 lists are "
+                    "--ivf-list-dtype fp8")
         if args.nlist < 1 or not 1 <= args.nprobe <= min(args.nlist, 1024):
             p.error(f"--index ivf needs --nlist >= 1 and 1 <= --nprobe <= min(nlist, 1024), "
                     f"not nlist={args.nlist} nprobe={args.nprobe}")

@@ -118,7 +118,9 @@ def predict_dense(args, k=100):
     ``args.index == "ivf"`` (main.py --index): the shard becomes an ``IVFDenseIndex`` of
     ``args.nlist`` lists, each rank training over its own slice, and a search ranks the rows
     of the ``args.nprobe`` lists nearest to each claim (per shard); the recall line names
-    both.  With every list probed it is the flat index's ranking."""
+    both.  With every list probed it is the flat index's ranking.  ``args.ivf_list_dtype ==
+    "fp8"`` (main.py --ivf-list-dtype) keeps the lists as e4m3 bytes (``train(dtype="fp8")``);
+    the recall line then names that too."""
     from irc_amd.retrieval import IVFDenseIndex, shard_bounds
 
     assert args.ckpt is not None
@@ -143,9 +145,12 @@ def predict_dense(args, k=100):
     ivf = getattr(args, "index", "flat") == "ivf"
     if ivf:
         if by_page or getattr(args, "index_dtype", "bf16") != "bf16":
-            raise ValueError("--index ivf: bf16 lists and the line unit only")
+            raise ValueError("--index ivf: --index-dtype bf16 (e4m3 lists are "
+                             "--ivf-list-dtype fp8) and the line unit only")
+        list_dtype = getattr(args, "ivf_list_dtype", "bf16")
         index = IVFDenseIndex.train(encode_corpus(model, texts[lo:hi], args.device), args.nlist,
-                                    doc_offset=lo, group=group, seed=getattr(args, "seed", 0))
+                                    doc_offset=lo, group=group, seed=getattr(args, "seed", 0),
+                                    dtype=list_dtype)
     else:
         index = ShardedDenseIndex(encode_corpus(model, texts[lo:hi], args.device), doc_offset=lo,
                                   group=group, dtype=getattr(args, "index_dtype", "bf16"))
@@ -172,7 +177,8 @@ def predict_dense(args, k=100):
             hits += int(any(titles[j] in gold for j in row if j >= 0))
             total += 1
     if rank == 0:
-        unit = f" (ivf nlist={args.nlist} nprobe={args.nprobe})" if ivf else \
+        lists = " lists=fp8" if ivf and list_dtype == "fp8" else ""
+        unit = f" (ivf nlist={args.nlist} nprobe={args.nprobe}{lists})" if ivf else \
             (" (pages)" if by_page else "")
         print(f"evidence recall@{k}{unit}: {hits / max(total, 1):.4f}")
     return hits / max(total, 1)
